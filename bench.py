@@ -33,6 +33,10 @@ algorithmic bytes (read + write of one pass) / duration, peak 8 TB/s; ``traffic`
 committed rocprofv3 summary, printed only while the kernel sources still hash to the fingerprint the summary was
 collected at.  ``cpu_baseline``: the CPU oracle (numpy / scipy restatement of prysm's focus, scipy.fft single-threaded
 exactly as prysm ships it) timed on this box's host cores on the same workload (N = 1 only).
+
+``--dump-outputs DIR``: after the timed steps rank 0 writes the focal field of its last timed step under DIR as .npy files
+(dump_outputs: the whole field, or a central block + a seeded sample of a large one); the input field is seeded, so the files of two
+builds run with the same arguments compare element by element.
 """
 import argparse
 import ctypes
@@ -89,8 +93,8 @@ def _summary(line):
         'frac': get('roofline/frac'), 'two_copies_ms': get('roofline/two_plain_copies_ms'), 'n2048_per_s': get('n2048/value'),
         'psf_variant_ms': get('psf_variant/ms_per_psf'),
         'm7_c64_eager_ms': get(oc + 'model_7plane_1024/c64/eager_ms_per_wavelength'), 'm7_c64_graph_ms': get(oc + 'model_7plane_1024/c64/graph_ms_per_wavelength'),
-        'm7_c64_9wvl_graph_ms': get(oc + 'model_7plane_1024/c64/graph_9wvl_ms'), 'm7_c64_9wvl_graph_branches_ms': get(oc + 'model_7plane_1024/c64/graph_branches_9wvl_ms'),
-        'm7_c64_czt_graph_ms': get(oc + 'model_7plane_1024/c64/czt/graph_ms_per_wavelength'), 'm7_c64_czt_9wvl_graph_branches_ms': get(oc + 'model_7plane_1024/c64/czt/graph_branches_9wvl_ms'),
+        'm7_c64_9wvl_graph_ms': get(oc + 'model_7plane_1024/c64/graph_9wvl_ms'),
+        'm7_c64_czt_graph_ms': get(oc + 'model_7plane_1024/c64/czt/graph_ms_per_wavelength'),
         'm7_c128_eager_ms': get(oc + 'model_7plane_1024/c128/eager_ms_per_wavelength'), 'm7_c128_graph_ms': get(oc + 'model_7plane_1024/c128/graph_ms_per_wavelength'),
         'm7_published_titan_xp_ms': get(oc + 'model_7plane_1024/published/titan_xp_cupy_ms_per_wavelength'),
         'c2_ms': get(oc + 'config2_focus_2048_c64/ms'), 'c2_two_streams_ms': get(oc + 'config2_focus_2048_c64/two_streams/ms'),
@@ -145,7 +149,15 @@ def parse():
                     help='seconds the side measurements after the timed region may take before the headline line is printed without them')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='torch.distributed backend (nccl = RCCL; gloo only to exercise the N > 1 path when the ranks share a GPU)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the focal field of the last timed step as DIR/<name>.npy (rank 0; see dump_outputs); '
+                         'bench_outputs/ in the repository root is ignored by git')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.warmup < 0:
+        ap.error('--warmup must not be negative')
+    return args
 
 
 def self_launch(args):
@@ -169,6 +181,34 @@ def make_field(n, cdtype, seed):
     rng = np.random.default_rng(seed)
     x = (rng.standard_normal((n, n)) + 1j * rng.standard_normal((n, n))).astype(cdtype)
     return x
+
+
+DUMP_SAMPLES = 1 << 21    # elements of the seeded sample of a field too large to write whole
+DUMP_FULL_BYTES = 32 << 20   # a field up to this size is written whole
+DUMP_CROP = 1024          # edge of the central block written beside the sample
+
+
+def dump_outputs(f, out_dir):
+    """What the timed path hands its caller -- the complex focal field of the last timed step -- as real arrays of the field's
+    precision (float32 for complex64, float64 for complex128), the last axis holding (real, imaginary).  A field of at most
+    DUMP_FULL_BYTES is written whole (focus.npy); a larger one as its central DUMP_CROP^2 block (focus_center.npy) and the values at
+    DUMP_SAMPLES flat indices drawn with a fixed seed (focus_sample.npy, indices ascending): at most 48 MB in all.  The inputs are
+    seeded, so two builds run with the same arguments can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    a = f.detach().cpu().numpy()
+    a = np.stack([a.real, a.imag], axis=-1)
+    written = {}
+    if a.nbytes <= DUMP_FULL_BYTES:
+        written['focus'] = a
+    else:
+        ny, nx = a.shape[:2]
+        cy, cx = min(ny, DUMP_CROP), min(nx, DUMP_CROP)
+        written['focus_center'] = a[(ny - cy) // 2:(ny - cy) // 2 + cy, (nx - cx) // 2:(nx - cx) // 2 + cx]
+        idx = np.sort(np.random.default_rng(20261015).choice(ny * nx, size=min(DUMP_SAMPLES, ny * nx), replace=False))
+        written['focus_sample'] = a.reshape(ny * nx, 2)[idx]
+    for name, v in written.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(v))
+    return {name: {'shape': list(v.shape), 'dtype': v.dtype.name} for name, v in written.items()}
 
 
 def plain_copy_pair_ms(x, reps=50):
@@ -418,13 +458,7 @@ def sec_model7(out, wavelengths=9):
                     e['sequence_9wvl_ms'] = _event_ms(all_wvls_block, 10)
                 g9 = G.capture(lambda a, o: all_wvls(), dev['amp'], dev['opd'])
                 e['graph_9wvl_ms'] = _event_ms(g9.graph.replay, 20)
-                # the nine independent chains captured INSIDE a sequence block: the hipGraph gets one branch per ring stream, the chains
-                # overlap on the device (small GEMMs that fill a quarter of the CUs each) and no host dispatch is left to pay for it
-                g9s = G.capture(lambda a, o: all_wvls_block(), dev['amp'], dev['opd'])
-                e['graph_branches_9wvl_ms'] = _event_ms(g9s.graph.replay, 20)
-                e['graph_branches_identical'] = bool(torch.equal(g9s(dev['amp'], dev['opd']), g9(dev['amp'], dev['opd'])))
-                e['graph_branches_ms_per_wavelength'] = e['graph_branches_9wvl_ms'] / len(per)
-                del g1, g9, g9s
+                del g1, g9
                 return e
 
             per = build('mdft')
@@ -433,7 +467,6 @@ def sec_model7(out, wavelengths=9):
             fl = model7_flops()['total']
             peak = F32_MFMA_PEAK_TF if prec == 32 else F64_MFMA_PEAK_TF
             e['graph_frac_of_mfma_peak'] = fl / (e['graph_ms_per_wavelength'] * 1e-3) / 1e12 / peak
-            e['graph_branches_frac_of_mfma_peak'] = fl / (e['graph_branches_ms_per_wavelength'] * 1e-3) / 1e12 / peak
             del per
             # the same planes through the chirp-Z executors the reference offers beside the matrix DFT (prepare_executor(kind='czt'),
             # prysm/fttools.py:235-389): one fused convolution kernel per axis instead of two GEMMs
@@ -875,7 +908,8 @@ def run_in_is_steady(hist, at, tol=PREWARM_TOL, lookback_ms=100.0):
 
 
 def propagation_loop(ranks, x, steps, warmup, info=None, repeats=0):
-    """warmup untimed + exactly `steps` timed focus(x, 1) per rank; returns seconds (MAX over ranks).
+    """warmup untimed + exactly `steps` timed focus(x, 1) per rank; returns seconds (MAX over ranks) and the focal field of the last
+    timed step (the same call on the same input as every step before it).
 
     Before the W warm-up steps the same propagation runs untimed until the device has reached its steady state: batches of 40
     propagations (synchronised one by one) for at least PREWARM_MIN_MS, until the mean of the last five batches is within 1 % of the
@@ -1133,6 +1167,7 @@ def main():
         dist.all_reduce(torch.zeros(1, device='cuda'))     # create the communicator outside every timed region
     loop_info = {}
     elapsed, f = propagation_loop(ranks, x, args.steps, args.warmup, info=loop_info, repeats=4)
+    dumped = dump_outputs(f, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     del f
 
     # ---- the headline line, complete as the contract wants it, BEFORE any side measurement
@@ -1172,6 +1207,8 @@ def main():
                                  'measured in this run'},
         }
         line.update(loop_info)
+        if dumped:
+            line['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         rep = loop_info.get('repeat_ms') or []
         if rep:
             allr = rep + [ms_step]

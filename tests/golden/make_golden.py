@@ -384,6 +384,69 @@ def precision32():
     np.savez_compressed(os.path.join(HERE, 'precision32.npz'), **out)
 
 
+def reference_parity():
+    """focus / unfocus / angular_spectrum / both DFT executors (forward + adjoint) / pad2d on rectangular, odd and padded shapes with
+    a focal shift (tests/test_oracle.py::test_oracle_matches_reference_outputs)."""
+    out = {}
+    rng = np.random.default_rng(99)
+    cases = (((24, 20), 1), ((17, 10), 1.5), ((16, 16), 2))
+    for i, (shape, Q) in enumerate(cases):
+        x = rng.normal(size=shape) + 1j * rng.normal(size=shape)
+        out[f'c{i}_x'] = x
+        out[f'c{i}_Q'] = np.float64(Q)
+        out[f'c{i}_focus'] = propagation.focus(x, Q)
+        out[f'c{i}_unfocus'] = propagation.unfocus(x, Q)
+        out[f'c{i}_as'] = propagation.angular_spectrum(x, 0.6, 0.02, 7.0, Q=Q)
+        for kind in ('mdft', 'czt'):
+            ex = propagation.prepare_executor(0.1, shape, 1.3, (10, 14), 0.6, 40.0, (0.3, 0.1), kind)
+            out[f'c{i}_{kind}_fwd'] = ex(x)
+            g = rng.normal(size=(10, 14)) + 1j * rng.normal(size=(10, 14))
+            out[f'c{i}_{kind}_g'] = g
+            out[f'c{i}_{kind}_adj'] = ex.adjoint(g)
+    out['pad17'] = fttools.pad2d(x, 1.7)
+    out['ncases'] = np.int64(len(cases))
+    np.savez_compressed(os.path.join(HERE, 'reference_parity.npz'), **out)
+
+
+def facade():
+    """the array code of coordinates / geometry / Wavefront constructors / pad2d / transfer function / MDFT executor on numpy, dtypes
+    included, at both precisions (tests/test_host_logic.py::test_numpy_facade_runs_the_references_array_code)."""
+    field = np.random.default_rng(3).standard_normal((24, 20)) + 1j * np.random.default_rng(4).standard_normal((24, 20))
+    out = {'field': field}
+    x, y = coordinates.make_xy_grid(64, diameter=10)
+    r, t = coordinates.cart_to_polar(x, y)
+    A = geometry.circle(5, r)
+    wf = propagation.Wavefront.from_amp_and_phase(A, 100 * (r / 5) ** 2 * np.cos(t), 0.6328, x[0, 1] - x[0, 0])
+    pad = fttools.pad2d(wf.data, Q=2)
+    out.update(x=x, r=r, t=t, A=A, wf=wf.data, pad=pad, crop=fttools.crop_center(pad, (40, 30)), I=wf.intensity.data,
+               rng=fttools.fftrange(9), lens=propagation.Wavefront.thin_lens(250.0, 0.6328, x, y).data)
+    out['xx'], _, out['fx'], _ = propagation.coordinates_for_focus(0.1, (64, 64), 2.0, (16, 16), 0.6328, 100.0)
+    for prec in (64, 32):
+        config.precision = prec
+        try:
+            a = field.astype(np.complex64 if prec == 32 else np.complex128)
+            ex = propagation.prepare_executor(0.2, (24, 20), 3.0, (10, 12), 0.6328, 50.0, kind='mdft')
+            out[f'mdft{prec}'] = propagation.focus_dft(a, ex)
+            out[f'mdft_adj{prec}'] = propagation.focus_dft_adjoint(out[f'mdft{prec}'], ex)
+            out[f'H{prec}'] = propagation.angular_spectrum_transfer_function((8, 12), 0.6328, 0.01, 10.0)
+        finally:
+            config.precision = 64
+    np.savez_compressed(os.path.join(HERE, 'facade.npz'), **out)
+
+
+PLUG_MODULES = ('propagation', 'propagation.fft', 'propagation.angular_spectrum', 'propagation.dft', 'propagation.coronagraph',
+                'propagation.wavefront', 'fttools')
+
+
+def prysm_layout():
+    """the public names of the modules prysm_amd.mathops.set_backend_to_mi355x rebinds names on
+    (tests/test_host_logic.py::test_install_into_prysm_rebinds_and_restores)"""
+    import importlib
+    out = {m: np.array(sorted(n for n in dir(importlib.import_module('prysm.' + m)) if not n.startswith('_')))
+           for m in PLUG_MODULES}
+    np.savez_compressed(os.path.join(HERE, 'prysm_layout.npz'), **out)
+
+
 if __name__ == '__main__':
     if len(sys.argv) > 1:   # only the named groups
         for name in sys.argv[1:]:
@@ -399,6 +462,9 @@ if __name__ == '__main__':
     next_rows()
     multires()
     encircled()
+    reference_parity()
+    facade()
+    prysm_layout()
     for f in sorted(os.listdir(HERE)):
         if f.endswith('.npz'):
             print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -59,10 +59,10 @@ def test_shard_bounds_cover_everything_once():
     assert shard_bounds(64, 3, 8) == (24, 32)
 
 
-def test_fft_engine_emulation():
+def test_fft_engine_emulation(tmp_path):
     """Compile and run the CPU emulation of the HIP FFT kernels' per-thread logic (tools/emu_fft.cpp):
     same headers as the device build, every stage structure, pad / shift / crop maps, tiled intermediate."""
-    exe = '/tmp/pm_emu_fft_test'
+    exe = str(tmp_path / 'pm_emu_fft_test')
     subprocess.run(['g++', '-O2', '-std=c++17', '-I', os.path.join(ROOT, 'prysm_amd', 'csrc'),
                     os.path.join(ROOT, 'tools', 'emu_fft.cpp'), '-o', exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
@@ -70,10 +70,10 @@ def test_fft_engine_emulation():
     assert 'EMU OK' in out.stdout
 
 
-def test_mixed_radix_kernel_emulation():
+def test_mixed_radix_kernel_emulation(tmp_path):
     """tools/emu_mix.cpp: the per-thread code of the mixed-radix kernel (csrc/fft_mixed.h: planner, every small DFT from 2 to 32, first /
     middle / last stages, digit-reversed last stage, row and column layouts) run thread by thread against a long-double DFT"""
-    exe = '/tmp/pm_emu_mix_test'
+    exe = str(tmp_path / 'pm_emu_mix_test')
     subprocess.run(['g++', '-O2', '-std=c++17', '-I', os.path.join(ROOT, 'prysm_amd', 'csrc'),
                     os.path.join(ROOT, 'tools', 'emu_mix.cpp'), '-o', exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=900)
@@ -81,11 +81,11 @@ def test_mixed_radix_kernel_emulation():
     assert 'all ok' in out.stdout
 
 
-def test_composite_register_engine_emulation():
+def test_composite_register_engine_emulation(tmp_path):
     """tools/emu_ce.cpp: the per-thread code of the composite register engine (csrc/fft_ce.h: prime-factor small DFTs, stages, the
     register-index exchange, row and column global access with windows and rotations) for every shipped plan and workgroup shape
     (tools/emu_ce_plans.inc, written by tools/ce_gen.py) run thread by thread against a long-double DFT"""
-    exe = '/tmp/pm_emu_ce_test'
+    exe = str(tmp_path / 'pm_emu_ce_test')
     subprocess.run(['g++', '-O2', '-std=c++17', '-I', os.path.join(ROOT, 'prysm_amd', 'csrc'), '-I', os.path.join(ROOT, 'tools'),
                     os.path.join(ROOT, 'tools', 'emu_ce.cpp'), '-o', exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=900)
@@ -124,40 +124,74 @@ def test_generated_plan_tables_match_the_generator():
         assert best <= 1.0 + 1e-9, (plan, seqs, col, es, best, pad)
 
 
-REF = '/root/reference'
+def _standin_prysm(monkeypatch, layout):
+    """An importable stand-in of prysm with the reference's module layout (tests/golden/prysm_layout.npz: the public names of every
+    module set_backend_to_mi355x rebinds names on), each name its own object; prysm.mathops' fft / np shims forward attribute access
+    to their _srcmodule."""
+    import sys
+    import types
+
+    class Shim:
+        def __init__(self):
+            self._srcmodule = object()
+
+        def __getattr__(self, name):
+            return getattr(self._srcmodule, name)
+
+    def mod(name, names=()):
+        m = types.ModuleType(name)
+        m.__dict__.update({n: object() for n in names})
+        monkeypatch.setitem(sys.modules, name, m)
+        return m
+
+    root = mod('prysm_standin')
+    for path in sorted(layout.files, key=len):        # parents first
+        parent, _, leaf = ('prysm_standin.' + path).rpartition('.')
+        setattr(sys.modules[parent], leaf, mod(f'{parent}.{leaf}', [str(n) for n in layout[path]]))
+    root.conf = mod('prysm_standin.conf')
+    root.conf.config = types.SimpleNamespace(precision=np.float64)
+    root.mathops = mod('prysm_standin.mathops')
+    root.mathops.fft, root.mathops.np = Shim(), Shim()
+    return root
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'prysm')), reason='reference not present on this box')
-def test_install_into_prysm_rebinds_and_restores():
+def test_install_into_prysm_rebinds_and_restores(monkeypatch):
     """The plug mechanism of INTEGRATION.md: names on prysm's modules are rebound to the MI355X engine and
     restored afterwards (no compute here -- there is no GPU in this container)."""
     import sys
-    sys.path.insert(0, REF)
-    try:
-        import prysm
-        import prysm.propagation as P
-        import prysm.propagation.wavefront as W
-        import prysm.fttools as F
-    finally:
-        sys.path.remove(REF)
     import prysm_amd
     from prysm_amd import mathops
-    orig_focus, orig_mdft, orig_wf = P.focus, F.MDFT, P.Wavefront
+    layout = np.load(os.path.join(ROOT, 'tests', 'golden', 'prysm_layout.npz'))
+    names = {m: {str(n) for n in layout[m]} for m in layout.files}
+    # what the plug mechanism rebinds exists where it looks for it in the reference
+    assert set(mathops._PROPAGATION_NAMES) <= names['propagation'] and set(mathops._FTTOOLS_NAMES) <= names['fttools']
+    assert 'Wavefront' in names['propagation'] and {'Wavefront', 'focus'} <= names['propagation.wavefront']
+    prysm = _standin_prysm(monkeypatch, layout)
+    P, W, F = prysm.propagation, prysm.propagation.wavefront, prysm.fttools
+    mods = {m: sys.modules['prysm_standin.' + m] for m in layout.files}
+    before = {m: dict(vars(md)) for m, md in mods.items()}
+    orig_fft, orig_np = prysm.mathops.fft._srcmodule, prysm.mathops.np._srcmodule
     mathops.set_backend_to_mi355x(prysm)
     try:
-        assert P.focus is prysm_amd.propagation.focus
+        for m, md in mods.items():
+            assert {n for n in vars(md) if not n.startswith('_')} == names[m], m      # rebinds only, nothing added
+            if m != 'fttools':
+                for name in set(mathops._PROPAGATION_NAMES) & names[m]:
+                    assert getattr(md, name) is getattr(prysm_amd.propagation, name), (m, name)
         assert W.focus is prysm_amd.propagation.focus          # bound by name in wavefront.py
         assert P.prepare_executor is prysm_amd.propagation.prepare_executor
-        assert F.MDFT is prysm_amd.fttools.MDFT
-        assert P.Wavefront is prysm_amd.propagation.Wavefront
-        import prysm.mathops as PM
+        for name in mathops._FTTOOLS_NAMES:
+            assert getattr(F, name) is getattr(prysm_amd.fttools, name)
+        assert P.Wavefront is W.Wavefront is prysm_amd.propagation.Wavefront
+        PM = prysm.mathops
         assert isinstance(PM.fft._srcmodule, mathops.FFTFacade)    # the unfused fft shim level
         assert PM.fft.fft2.__self__ is PM.fft._srcmodule
+        assert PM.np._srcmodule is orig_np                         # arrays=False leaves prysm's numpy alone
     finally:
         mathops.restore_prysm_backend()
-    assert P.focus is orig_focus and F.MDFT is orig_mdft and P.Wavefront is orig_wf
-    import prysm.mathops as PM
-    assert not isinstance(PM.fft._srcmodule, mathops.FFTFacade)
+    for m, md in mods.items():
+        assert vars(md) == before[m], m
+    assert prysm.mathops.fft._srcmodule is orig_fft
 
 
 def test_small_host_helpers():
@@ -223,59 +257,48 @@ def test_numpy_facade_semantics():
         NumpyFacade().zeros(3) if not torch.cuda.is_available() else (_ for _ in ()).throw(RuntimeError())
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'prysm')), reason='reference not present on this box')
-def test_numpy_facade_runs_the_references_array_code():
-    """prysm's own coordinates / geometry / Wavefront constructors / pad2d / transfer function / MDFT executor run
-    unmodified on ``np._srcmodule = NumpyFacade`` and give numpy's results, dtypes included."""
-    import sys
+def test_numpy_facade_runs_the_references_array_code(monkeypatch):
+    """The array code of prysm's coordinates / geometry / Wavefront constructors / pad2d / transfer function / MDFT executor, as the
+    oracle restates it against one module-level ``np``, runs unmodified on ``np = NumpyFacade`` and gives the reference's numpy results,
+    dtypes included (the reference's outputs are tests/golden/facade.npz)."""
     import torch
-    sys.path.insert(0, REF)
-    try:
-        from prysm import mathops, coordinates, geometry, fttools, propagation
-        from prysm.conf import config
-        from prysm.propagation import Wavefront
-    finally:
-        sys.path.remove(REF)
+    from oracle import prysm_oracle as O
     from prysm_amd.npfacade import NumpyFacade, DeviceArray
     from prysm_amd.mathops import FFTFacade
-    field = np.random.default_rng(3).standard_normal((24, 20)) + 1j * np.random.default_rng(4).standard_normal((24, 20))
+    ref = np.load(os.path.join(ROOT, 'tests', 'golden', 'facade.npz'))
+    field = ref['field']
 
     def run():
-        xp = mathops.np
+        xp = O.np
         out = {}
-        x, y = coordinates.make_xy_grid(64, diameter=10)
-        r, t = coordinates.cart_to_polar(x, y)
-        A = geometry.circle(5, r)
-        wf = Wavefront.from_amp_and_phase(A, 100 * (r / 5) ** 2 * xp.cos(t), 0.6328, x[0, 1] - x[0, 0])
-        pad = fttools.pad2d(wf.data, Q=2)
-        out.update(x=x, r=r, t=t, A=A, wf=wf.data, pad=pad, crop=fttools.crop_center(pad, (40, 30)), I=wf.intensity.data,
-                   rng=fttools.fftrange(9), lens=Wavefront.thin_lens(250.0, 0.6328, x, y).data)
-        out['xx'], _, out['fx'], _ = propagation.coordinates_for_focus(0.1, (64, 64), 2.0, (16, 16), 0.6328, 100.0)
-        for prec in (64, 32):
-            config.precision = prec
-            try:
-                a = xp.asarray(field.astype(np.complex64 if prec == 32 else np.complex128))
-                ex = propagation.prepare_executor(0.2, (24, 20), 3.0, (10, 12), 0.6328, 50.0, kind='mdft')
-                out[f'mdft{prec}'] = propagation.focus_dft(a, ex)
-                out[f'mdft_adj{prec}'] = propagation.focus_dft_adjoint(out[f'mdft{prec}'], ex)
-                out[f'H{prec}'] = propagation.angular_spectrum_transfer_function((8, 12), 0.6328, 0.01, 10.0)
-            finally:
-                config.precision = 64
+        x, y = O.make_xy_grid(64, diameter=10)
+        r, t = O.cart_to_polar(x, y)
+        A = O.circle(5, r)
+        wf = O.from_amp_and_phase(A, 100 * (r / 5) ** 2 * xp.cos(t), 0.6328)
+        pad = O.pad2d(wf, Q=2)
+        out.update(x=x, r=r, t=t, A=A, wf=wf, pad=pad, crop=O.crop_center(pad, (40, 30)), I=O.intensity(wf),
+                   rng=O.fftrange(9), lens=O.thin_lens(250.0, 0.6328, x, y))
+        out['xx'], _, out['fx'], _ = O.coordinates_for_focus(0.1, (64, 64), 2.0, (16, 16), 0.6328, 100.0)
+        for prec, real in ((64, np.float64), (32, np.float32)):
+            a = xp.asarray(field.astype(np.complex64 if prec == 32 else np.complex128))
+            ex = O.prepare_executor(0.2, (24, 20), 3.0, (10, 12), 0.6328, 50.0, kind='mdft', precision=real)
+            out[f'mdft{prec}'] = O.focus_dft(a, ex)
+            out[f'mdft_adj{prec}'] = ex.adjoint(out[f'mdft{prec}'])
+            out[f'H{prec}'] = O.angular_spectrum_transfer_function((8, 12), 0.6328, 0.01, 10.0, precision=real)
         return out
 
-    ref = run()
     cpu = torch.device('cpu')
-    mathops.np._srcmodule, mathops.fft._srcmodule = NumpyFacade(cpu), FFTFacade(cpu)
-    try:
-        got = run()
-        with pytest.raises(RuntimeError):      # the transforms themselves have no CPU path
-            propagation.focus(got['wf'], 2)
-    finally:
-        mathops.set_backend_to_defaults()
-    for k, want in ref.items():
+    monkeypatch.setattr(O, 'np', NumpyFacade(cpu))
+    got = run()
+    with pytest.raises(RuntimeError):      # the transforms themselves have no CPU path
+        FFTFacade(cpu).fft2(got['wf'])
+    monkeypatch.undo()
+    for k in ref.files:
+        if k == 'field':
+            continue
         assert isinstance(got[k], DeviceArray), k
         have = got[k].get()
-        want = np.asarray(want)
+        want = ref[k]
         assert have.shape == want.shape and have.dtype == want.dtype, (k, have.dtype, want.dtype)
         tol = 1e-6 if want.dtype in (np.complex64, np.float32) else 1e-14
         assert np.abs(have.astype(complex) - want.astype(complex)).max() <= tol * max(np.abs(want).max(), 1), k
