@@ -39,7 +39,7 @@ struct Fft2Plan {
     int64_t chunk;        // fields per launch pair: the intermediates of one chunk stay resident in the 256 MiB
                           // Infinity Cache between the two passes, consecutive chunks reuse the same workspace
     bool fold;            // one radix-2 step of the column transform is taken in the row pass (RowStoreFold): the column
-                          // pass then runs two planes of M/2-point tiles
+                          // pass then runs two planes of M/2-point tiles; on the transposed Hermitian form (r2c_t) in the column pass's load
     bool mix_n, mix_m;    // the row / column transforms take the mixed-radix kernel (composite lengths, fft_mixed.hip)
     bool mix_fold;        // ... with one radix-2 step of the column transform folded into the row pass (MixRowOut fold_h): half-length column tiles
     int64_t w_ld;         // row pitch of the NATURAL intermediate (tc == 0), in elements: N, or N rounded up to whole 128 B lines when the
@@ -51,6 +51,9 @@ struct Fft2Plan {
     bool blue_big;        // blue2d whose convolution length exceeds the engine's: two big power-of-two transforms around the multiply
     bool blue2d;          // both axes: chirp multiply -> ONE fused fft2 x (B1 (x) B2) ifft2 chain of size MB1 x MB2 -> chirp multiply
                           // (blue2d_run); the workspace is then [a (M x N) | c (M x N) | workspace of the fused chain]
+    bool blue_fuse;       // ... with the chirp multiplies inside the chain's first / last row pass (blue2d_fused_run)
+    // launch choices (the runner reads these, not the knobs): log2 of the layout tile, sibling groups, row tiling, streaming loads / stores
+    int ltl, row_log_g, col_log_g, row_var, nt_in, nt_out;
 };
 
 // ---------------------------------------------------------------- fused fft2 -> multiply -> ifft2
@@ -63,6 +66,7 @@ struct FusedPlan {
     bool fold;                   // radix-2 step of the column transforms folded into the first / last row pass
     bool mixmid;                 // composite column length: natural intermediates of pitch w_ld, the mixed-radix middle pass (fft_mixed.h)
     int64_t w_ld;
+    int ltl, row_log_g, col_log_g, colmul_mode, nt_in, nt_out;     // launch choices, as in Fft2Plan (colmul_mode: knob of launch_col_mul)
 };
 
 // ---- real object, real result: the chain on half spectra (fft_c2r.h)
@@ -70,10 +74,10 @@ struct HermConvPlan {
     int logn, logm, tc, log_k;
     bool fold;          // radix-2 step of the column transforms in the first / last row pass, as in the complex chain
     size_t ws_bytes;
+    int ltl, row_log_g, col_log_g, nt_out;     // launch choices, as in Fft2Plan
 };
 
 // ---- capi_plan.hip / capi_run.hip
-int sibling_log_g(int log_k);
 inline AxisMap to_map(const pm_axis& a) { return AxisMap{int(a.n), int(a.len), int(a.off), int(a.shift)}; }
 int64_t batch_chunk(int64_t nb, size_t ws_field);
 Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c = true);

@@ -5,10 +5,37 @@ namespace pm {
 
 // sibling group of column-pass workgroups: the tiles of one layout-tile row, at most 8
 // (knob col_log_g >= 0 overrides: up to 2^5 = the 32 workgroups an XCD's CUs hold at one per CU -- experiments of round 5)
-int sibling_log_g(int log_k) {
+static int sibling_log_g(int log_k) {
     if (tuning().col_log_g >= 0) return tuning().col_log_g > 5 ? 5 : tuning().col_log_g;
     return log_k < 1 ? 1 : (log_k > 3 ? 3 : log_k);
 }
+
+// log2 of a power of two (the layout tile tc << log_k); 0 for 0
+static int log2_pow2(int64_t v) { int l = 0; while ((int64_t(1) << l) < v) ++l; return l; }
+
+// layout tile width TL = tc << log_k, auto: >= 256 B pieces from 4096 columns
+static int auto_log_k(int64_t N) { return N >= 8192 ? 3 : (N >= 4096 ? 2 : 1); }
+
+// streaming (non-temporal) input loads: 0 off, 1 on, auto once the input no longer fits beside the intermediate
+static int nt_in_for(size_t in_bytes) { return tuning().nt_in >= 0 ? tuning().nt_in : (in_bytes >= (size_t(96) << 20) ? 1 : 0); }
+
+// Streaming stores, two measured rules.  The column store of the two-pass transform (ColStoreNat): they only help when a workgroup
+// writes whole 64 B pieces -- on the 32 B pieces of 8192-point columns they defeat the L2 write combining of sibling workgroups
+// (measured: 977 -> 428 us without) --, and only while the output is about the size of the 256 MiB Infinity Cache: measured +25 % at
+// 256 MiB (4096^2 complex128), -10 % at 512 MiB and 1 GiB (8192^2), -8 % at 128 MiB.  logm_tile: log2 of the column tile, -1 = the output's.
+static int col_store_nt(const pm_fft2_desc* d, int logm_tile) {
+    if (tuning().nt_out >= 0) return tuning().nt_out;
+    const size_t oes = (d->dtype == PM_C64 ? 8 : 16) / (d->epilogue == PM_EPI_NONE ? 1 : 2);
+    const size_t out_bytes = size_t(d->batch > 1 ? d->batch : 1) * size_t(d->out_y.len) * size_t(d->out_x.len) * oes;
+    if (logm_tile < 0) logm_tile = engine_log2(d->out_y.n) >= 0 ? engine_log2(d->out_y.n) : 12;
+    const size_t piece = size_t(col_tile_width_for(d->dtype, logm_tile, 0)) * oes;
+    return (out_bytes >= (size_t(192) << 20) && out_bytes < (size_t(384) << 20) && piece >= 64) ? 1 : 0;
+}
+// The last row pass of the fused chains writes the output once, in whole rows, and every line it does not leave in the caches is a line of
+// the intermediate that stays.  Measured (profiles/r03/exp_nt_rows.log, chain us without / with): 4096^2 complex128 (256 MiB out)
+// 344-347 / 320-321, padded 2048^2 -> 4096^2 complex128 343 / 326, 4096^2 complex64 (128 MiB) 167.7 / 163.3, 2048^2 complex64 54.6 / 52.7,
+// 2048^2 complex128 83.0 / 82.8.  Not beyond the Infinity Cache's size class (the column store's -10 % at 512 MiB and 1 GiB above).
+static int row_store_nt(size_t out_bytes) { return tuning().nt_out >= 0 ? tuning().nt_out : (out_bytes >= (size_t(24) << 20) && out_bytes < (size_t(384) << 20)); }
 
 
 static int check_axis(const pm_axis& a, const char* name) {
@@ -24,12 +51,16 @@ static int check_axis(const pm_axis& a, const char* name) {
 // load / butterfly / store phases overlap), twice the register budget per thread (complex128) and 64 B instead of 32 B
 // pieces at 8192.  Measured (profiles/r01/tune_fold.log): 4096^2 complex64 101.9 -> 98.1 us, complex128 229 -> 216 us,
 // 8192^2 complex64 557 -> 497 us, complex128 1143 -> 1047 us; 2048-point columns gain nothing (complex128 loses).
-static bool fold_legal(const pm_fft2_desc* d, int logn, int logm) {
+// fold_input_ok is the input side, which the fused chain shares.
+static bool fold_input_ok(const pm_fft2_desc* d, int logn, int logm) {
     const int64_t M = d->in_y.n;
-    return logn >= 11 && logm >= 3 && d->in_y.off == 0 && d->in_y.len == M && (d->in_y.shift == 0 || d->in_y.shift == M / 2) &&
-           (d->out_y.off % 2) == 0 && (d->out_y.len % 2) == 0 && (d->out_y.shift % 2) == 0 && d->mul_kind == PM_MUL_NONE &&
-           d->batch <= 1 && (d->out_ld % 2) == 0;
+    return logn >= 11 && logm >= 3 && d->in_y.off == 0 && d->in_y.len == M && (d->in_y.shift == 0 || d->in_y.shift == M / 2) && d->batch <= 1;
 }
+static bool fold_legal(const pm_fft2_desc* d, int logn, int logm) {
+    return fold_input_ok(d, logn, logm) && (d->out_y.off % 2) == 0 && (d->out_y.len % 2) == 0 && (d->out_y.shift % 2) == 0 &&
+           d->mul_kind == PM_MUL_NONE && (d->out_ld % 2) == 0;
+}
+static bool fold_auto(int logm) { return tuning().fold > 0 || (tuning().fold < 0 && logm >= 12); }     // knob fold: 1 wherever legal, 0 never
 
 // Hermitian path (fft_r2c.h): a FORWARD transform of an unpadded real field, both lengths on the engine (rows of at least 32
 // samples), rotations by 0 or half a length, an output that keeps every bin, no multiplier, one field.
@@ -49,18 +80,21 @@ static bool r2c_legal(const pm_fft2_desc* d, int logn, int logm) {
     return true;
 }
 
+// fold of the transposed form's column pass (a radix-2 step in the load, two workgroups per CU): from 4096 rows (knob herm_t_fold 1: 2048)
+static bool hermt_fold(int logm) { return (tuning().herm_t_fold > 0 && logm >= 11) || (tuning().herm_t_fold < 0 && logm >= 12); }
+
 // Transposed Hermitian form (fft_hermt.h): what r2c_legal accepts, with every rotation 0 or half a length (the input's become signs) and
-// lengths the two kernels exist for.  Auto (knob herm_t < 0), from profiles/r06/exp_herm_rule.log (mtf_from_psf, us, round-2 form /
-// transposed): fp32 128^2 21.1 / 17.0, 1024^2 30.3 / 19.8, 2048^2 38.8 / 32.5, 4096 x 1024 52.2 / 31.7, 4096^2 71.9 / 59.7,
-// 8192 x 2048 80.7 / 69.1 -- and 2048 x 8192 64.9 / 70.5, 4096 x 8192 122.9 / 155.4, 8192 x 4096 140.0 / 158.5: rows of 8192 samples
-// stay on the round-2 form, columns of 8192 beyond 2048 rows' width too; fp64 1024^2 29.4 / 22.3, 2048^2 41.8 / 40.1, 4096 x 2048
-// 67.8 / 58.4 -- and 2048 x 4096 64.7 / 76.5, 4096^2 117.8 / 156.1, 8192 x 2048 138.2 / 155.7: rows of 4096 complex128 points stay too.
+// lengths the two kernels exist for (fft_hermt_types.h, with the fold hermt_fold takes).  Auto (knob herm_t < 0), from
+// profiles/r06/exp_herm_rule.log (mtf_from_psf, us, round-2 form / transposed): fp32 128^2 21.1 / 17.0, 1024^2 30.3 / 19.8, 2048^2 38.8 /
+// 32.5, 4096 x 1024 52.2 / 31.7, 4096^2 71.9 / 59.7, 8192 x 2048 80.7 / 69.1 -- and 2048 x 8192 64.9 / 70.5, 4096 x 8192 122.9 / 155.4,
+// 8192 x 4096 140.0 / 158.5: rows of 8192 samples stay on the round-2 form, columns of 8192 beyond 2048 rows' width too; fp64 1024^2 29.4
+// / 22.3, 2048^2 41.8 / 40.1, 4096 x 2048 67.8 / 58.4 -- and 2048 x 4096 64.7 / 76.5, 4096^2 117.8 / 156.1, 8192 x 2048 138.2 / 155.7:
+// rows of 4096 complex128 points stay too.
 static bool hermt_legal(const pm_fft2_desc* d, int logn, int logm) {
     const int64_t M = d->in_y.n, N = d->in_x.n;
     const int ht = tuning().herm_t;
     if (ht == 0) return false;
-    if (logm < 5 || logm > 13 || logn < 5 || logn > (d->dtype == PM_C64 ? 13 : 12)) return false;
-    if (logm == 13 && tuning().herm_t_fold == 0) return false;     // 8192-point columns exist as planes of 4096-point tiles only
+    if (!hermt_col_kernel(d->dtype, logm, hermt_fold(logm)) || !hermt_row_kernel(d->dtype, logn)) return false;
     if (ht < 0 && (logn > (d->dtype == PM_C64 ? 12 : 11) || logm > (d->dtype == PM_C64 && logn <= 11 ? 13 : 12))) return false;
     if (!(d->in_y.shift == 0 || d->in_y.shift == M / 2) || !(d->out_y.shift == 0 || d->out_y.shift == M / 2) ||
         !(d->out_x.shift == 0 || d->out_x.shift == N / 2))
@@ -84,13 +118,20 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
     const int64_t rows = d->in_y.len;   // only stored input rows are transformed in pass 1
     p.fold = false;
     p.w_ld = N;
+    p.row_var = p.logn >= 0 ? row_variant(d->dtype, p.logn) : 0;
     p.r2c = allow_r2c && p.logn >= 0 && p.logm >= 0 && r2c_legal(d, p.logn, p.logm);
     p.r2c_t = p.r2c && hermt_legal(d, p.logn, p.logm);
     if (p.r2c_t) {
-        p.col_var = 0;
-        p.tc = 0;
-        p.log_k = 0;
+        p.col_var = p.tc = p.log_k = 0;
         p.ws_bytes = size_t(M / 2) * size_t(N) * es;      // rows u < M/2 of the column spectra, row-major (row 0 carries u = 0 and u = M/2)
+        p.fold = hermt_fold(p.logm);
+        if (tuning().herm_t_rowvar >= 0) p.row_var = tuning().herm_t_rowvar;
+        // adjacent tiles read the two halves of the input's 128 B lines and write adjacent lines of the intermediate: siblings on one XCD
+        // (profiles/r06/exp_herm_t_log_g.log, mtf_from_psf us at col_log_g 0 .. 5: 4096^2 fp32 folded 75.9 68.5 69.7 69.3 67.9 68.1 -- the pass reads
+        // 64 B pieces of a row-major array, neighbours share its 128 B lines --; 2048^2 (128 tiles, half the CUs) 31.9 33.6 33.7 33.8 34.2 34.4)
+        const int tcol = col_tile_width_for(d->dtype, p.fold ? p.logm - 1 : p.logm, 0), tiles = int((N / 2 + tcol - 1) / tcol);
+        p.col_log_g = tuning().col_log_g >= 0 ? tuning().col_log_g : (p.logm >= 12 ? 4 : 0);
+        while (p.col_log_g > 0 && ((p.fold ? 2 * tiles : tiles) % (8 << (p.col_log_g + (p.fold ? 1 : 0)))) != 0) --p.col_log_g;
     } else if (p.r2c) {
         p.col_var = 0;
         p.tc = col_tile_width_for(d->dtype, p.logm, 0);
@@ -111,18 +152,21 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
         while (p.log_k > 0 && ((N / 2) % (int64_t(p.tc) << p.log_k)) != 0) --p.log_k;
         const int64_t nc = N / 2, tl = int64_t(p.tc) << p.log_k;
         p.ws_bytes = size_t((nc + tl - 1) / tl) * size_t(M) * size_t(tl) * es;
+        p.col_log_g = sibling_log_g(p.log_k);
+        // folded: several rounds of one-workgroup-per-CU tiles (8192^2: 1024 of them): ALL 32 workgroups an XCD holds take adjacent tiles,
+        // so a row of the output is written 2 KiB at a time -- mtf_from_psf 8192^2 fp32 391 -> 373 us (exp_layout_sweep.log)
+        const int ntiles = int((nc + p.tc - 1) / p.tc);
+        if (p.fold && tuning().col_log_g < 0 && 2 * ntiles > 2 * pm_num_cus())
+            for (p.col_log_g = 5; p.col_log_g > 3 && ntiles % (8 << p.col_log_g); --p.col_log_g) {}
     } else if (p.logn >= 0 && p.logm >= 0) {
-        if (fold_legal(d, p.logn, p.logm)) {
-            const int f = tuning().fold;
-            p.fold = f > 0 || (f < 0 && p.logm >= 12);
-        }
+        p.fold = fold_legal(d, p.logn, p.logm) && fold_auto(p.logm);
         {   // 128 B tiles exist for 2048-point complex128 tiles only (fft_kernels.h launch_fft): the knob can switch them off or, for an
             // unfolded 2048-row transform, on -- nothing else
             const bool want2 = tuning().col_var >= 0 ? tuning().col_var == 2 : (p.fold && p.logm == 12);
             p.col_var = (want2 && d->dtype == PM_C128 && (p.fold ? p.logm - 1 : p.logm) == 11) ? 2 : 0;
         }
         p.tc = col_tile_width_for(d->dtype, p.fold ? p.logm - 1 : p.logm, p.col_var);
-        p.log_k = tuning().log_k >= 0 ? tuning().log_k : (N >= 8192 ? 3 : (N >= 4096 ? 2 : 1));   // auto: >= 256 B pieces from 4096 columns
+        p.log_k = tuning().log_k >= 0 ? tuning().log_k : auto_log_k(N);
         // folded 4096^2 complex64 (intermediate = 128 MiB, inside the Infinity Cache): 8 KiB row pieces measured 95.0 vs 97.8 us
         // (profiles/r01/tune_log_k.log); every other size / precision measured best with the narrow tiles above
         if (tuning().log_k < 0 && p.fold && d->dtype == PM_C64 && N == 4096 && M == 4096) p.log_k = 7;
@@ -130,9 +174,10 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
         const int64_t tl = int64_t(p.tc) << p.log_k;
         const int64_t ntl = (N + tl - 1) / tl;
         p.ws_bytes = size_t(ntl) * size_t(rows) * size_t(tl) * es;
+        p.col_log_g = sibling_log_g(p.log_k);
     } else {
-        p.tc = 0;
-        p.log_k = 0;
+        p.tc = p.log_k = 0;
+        p.col_log_g = 1;    // (the natural column pass's, when the columns are engine lengths)
         if (p.logm < 0 && use_mix(M)) {
             const int64_t line = int64_t(128 / es);
             p.w_ld = (N + line - 1) / line * line;
@@ -144,6 +189,10 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
     p.ws_field = (p.ws_bytes + 255) & ~size_t(255);
     p.chunk = batch_chunk(p.nbatch, p.ws_field);
     if (p.nbatch > 1) p.ws_bytes = p.ws_field * size_t(p.chunk);
+    p.ltl = log2_pow2(int64_t(p.tc) << p.log_k);
+    p.row_log_g = p.fold && !p.r2c_t ? 0 : tuning().row_log_g;      // the row pairs of a fold are not siblings: no XCD grouping
+    p.nt_in = nt_in_for(p.r2c ? size_t(M) * size_t(N) * es / 2 : size_t(p.nbatch) * size_t(rows) * size_t(d->in_x.len) * es);
+    p.nt_out = col_store_nt(d, p.fold ? p.logm - 1 : -1);
     // powers of two above the engine's longest transform: both axes powers of two, at least one split (big2d_run)
     p.big_rn = big_split2d(N);
     p.big_rm = big_split2d(M);
@@ -162,7 +211,7 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
     if (p.big_rn) {   // [Z: R_n planes of M x N/R_n | F (and the pre-processed rows before it): the same size]
         p.tc = 0;
         p.fold = false;
-        p.blue_n = p.blue_m = p.blue2d = p.blue_big = false;
+        p.blue_n = p.blue_m = p.blue2d = p.blue_big = p.blue_fuse = false;
         p.blue_off = 0;
         const size_t arr = (size_t(M) * size_t(N) * es + 255) & ~size_t(255);
         p.ws_bytes = 2 * arr;
@@ -195,6 +244,7 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
     p.blue2d = p.blue_n && p.blue_m && tuning().blue_2d && noflags;
     p.blue_big = !p.blue2d && tuning().blue_2d && noflags && blue_reach(N) && blue_reach(M) && (blue_needs_both(N, mixfit) || blue_needs_both(M, mixfit)) &&
                  (big_split(blue_conv_len(N)) > 1 || big_split(blue_conv_len(M)) > 1);
+    p.blue_fuse = p.blue2d && !p.blue_big && tuning().blue_fuse;
     if (p.blue_big) {   // [a (M x N) | c (M x N) | spectrum (MB1 x MB2) | workspace of the big transforms]
         p.blue2d = true;
         p.blue_n = p.blue_m = false;
@@ -236,36 +286,30 @@ bool plan_fused_mix(const pm_fft2_desc* d, FusedPlan& p) {
         const Fft2Plan pa = plan_fft2(&da);
         if (pa.tc != 0 || pa.w_ld != p.w_ld || pa.blue_n || pa.blue2d || pa.big_rn) return false;
     }
-    p.mixmid = true;
-    p.fold = false;
-    p.tc = 0;
-    p.log_k = 0;
+    p.mixmid = true;     // (plan_fused zeroed the fields this chain does not use)
     p.inplace = d->in_y.len == M;
     p.w1_bytes = (size_t(d->in_y.len) * size_t(p.w_ld) * es + 255) & ~size_t(255);
     p.w2_bytes = p.inplace ? 0 : ((size_t(M) * size_t(p.w_ld) * es + 255) & ~size_t(255));
     p.nbatch = p.chunk = 1;
     p.ws_bytes = p.w1_bytes + p.w2_bytes;
+    p.nt_out = row_store_nt(size_t(d->out_y.len) * size_t(d->out_x.len) * es);
     return true;
 }
 
 bool plan_fused(const pm_fft2_desc* d, FusedPlan& p) {
     const int64_t M = d->in_y.n, N = d->in_x.n;
+    p = FusedPlan{};
     p.logn = engine_log2(N);
     p.logm = engine_log2(M);
-    p.mixmid = false;
     p.w_ld = N;
     if (p.logm < 0) return plan_fused_mix(d, p);
     if (p.logn < 0) return false;
     const size_t es = d->dtype == PM_C64 ? 8 : 16;
-    // fold (see fold_legal): here the output window is unconstrained -- the last row pass rebuilds whole rows
-    p.fold = false;
-    if (p.logn >= 11 && p.logm >= 3 && d->in_y.off == 0 && d->in_y.len == M && (d->in_y.shift == 0 || d->in_y.shift == M / 2) &&
-        d->batch <= 1) {
-        const int f = tuning().fold;
-        p.fold = f > 0 || (f < 0 && p.logm >= 12);
-    }
+    // fold (see fold_legal): the input side only.  The output side is deliberately left out: the last row pass unfolds the row pairs and
+    // rebuilds whole rows before the output window and its rotation apply, and the multiplier is the chain's own middle pass
+    p.fold = fold_input_ok(d, p.logn, p.logm) && fold_auto(p.logm);
     p.tc = col_tile_width_for(d->dtype, p.fold ? p.logm - 1 : p.logm, 0);
-    p.log_k = tuning().log_k >= 0 ? tuning().log_k : (N >= 8192 ? 3 : (N >= 4096 ? 2 : 1));
+    p.log_k = tuning().log_k >= 0 ? tuning().log_k : auto_log_k(N);
     // folded 4096^2 complex64: 16 KiB row pieces measured 182.7 vs 188.7 us for the chain (see plan_fft2)
     if (tuning().log_k < 0 && p.fold && d->dtype == PM_C64 && N == 4096 && M == 4096) p.log_k = 8;
     while (p.log_k > 0 && (N % (int64_t(p.tc) << p.log_k)) != 0) --p.log_k;
@@ -278,6 +322,12 @@ bool plan_fused(const pm_fft2_desc* d, FusedPlan& p) {
     p.nbatch = d->batch > 1 ? d->batch : 1;
     p.chunk = batch_chunk(p.nbatch, p.w1_bytes + p.w2_bytes);
     p.ws_bytes = (p.w1_bytes + p.w2_bytes) * size_t(p.chunk);
+    p.ltl = log2_pow2(tl);
+    p.row_log_g = p.fold ? 0 : tuning().row_log_g;      // (as in plan_fft2)
+    p.col_log_g = sibling_log_g(p.log_k);
+    p.colmul_mode = tuning().colmul_mode;
+    p.nt_in = nt_in_for(size_t(p.nbatch) * size_t(d->in_y.len) * size_t(d->in_x.len) * es);
+    p.nt_out = row_store_nt(size_t(p.nbatch) * size_t(d->out_y.len) * size_t(d->out_x.len) * es);
     return true;
 }
 
@@ -389,6 +439,10 @@ bool herm_conv_plan(const pm_fft2_desc* d, HermConvPlan& p) {
     if ((N / 2) % p.tc) return false;
     const size_t es = d->dtype == PM_C64 ? 8 : 16;
     p.ws_bytes = size_t(M) * size_t(N / 2) * es;
+    p.ltl = log2_pow2(int64_t(p.tc) << p.log_k);
+    p.row_log_g = p.fold ? 0 : tuning().row_log_g;
+    p.col_log_g = sibling_log_g(p.log_k);
+    p.nt_out = row_store_nt(size_t(M) * size_t(N) * es / 2);
     return true;
 }
 
@@ -505,18 +559,21 @@ int pm_plan_explain(const pm_fft2_desc* d, int32_t op, char* buf, size_t n) {
         snprintf(buf, n, "fft2 %lldx%lld %s: route=%s conv=%lldx%lld ws=%zu", M, N, dt, p.blue_big ? "bluestein-2d-big" : "bluestein-2d",
                  (long long)blue_conv_len(M), (long long)blue_conv_len(N), p.ws_bytes);
     } else if (p.r2c_t) {
-        snprintf(buf, n, "fft2 %lldx%lld %s: route=hermitian-transposed cols=stockham-r2c(%lld) rows=stockham(%lld)x%lld ws=%zu", M, N, dt, M, N, M / 2, p.ws_bytes);
+        snprintf(buf, n, "fft2 %lldx%lld %s: route=hermitian-transposed cols=stockham-r2c(%lld) rows=stockham(%lld)x%lld ws=%zu g=%d%s", M, N, dt, M, N,
+                 M / 2, p.ws_bytes, p.col_log_g, p.fold ? " fold" : "");
     } else if (p.r2c) {
-        snprintf(buf, n, "fft2 %lldx%lld %s: route=hermitian%s rows=stockham-r2c(%lld) cols=stockham(%lld%s) tile=%d log_k=%d ws=%zu", M, N, dt,
-                 p.fold ? "-fold" : "", N / 2, p.fold ? M / 2 : M, p.fold ? "x2" : "", p.tc, p.log_k, p.ws_bytes);
+        snprintf(buf, n, "fft2 %lldx%lld %s: route=hermitian%s rows=stockham-r2c(%lld) cols=stockham(%lld%s) tile=%d log_k=%d ws=%zu g=%d", M, N, dt,
+                 p.fold ? "-fold" : "", N / 2, p.fold ? M / 2 : M, p.fold ? "x2" : "", p.tc, p.log_k, p.ws_bytes, p.col_log_g);
     } else {
         const bool en = p.logn >= 0, em = p.logm >= 0;
         // a composite axis whose length has a compile-time plan runs on the register engine (fft_ce.h) when the view is plain
         const bool ce_n = ce_rows_axis(d, p), ce_m = ce_cols_axis(d, p);
-        snprintf(buf, n, "fft2 %lldx%lld %s: route=%s rows=%s(%lld) cols=%s(%lld%s) tile=%d log_k=%d chunk=%lld ws=%zu", M, N, dt,
+        char g[16] = "";
+        if (p.tc) snprintf(g, sizeof g, " g=%d", p.col_log_g);     // the engine's tiled column pass
+        snprintf(buf, n, "fft2 %lldx%lld %s: route=%s rows=%s(%lld) cols=%s(%lld%s) tile=%d log_k=%d chunk=%lld ws=%zu%s", M, N, dt,
                  (en && em) ? (p.fold ? "engine-fold" : "engine") : ((p.mix_n || !p.blue_n) && (p.mix_m || !p.blue_m) && (p.mix_n || p.mix_m) ? "natural-mixed" : "natural"),
                  ce_n ? "mixed-radix-registers" : axis_route(en, p.mix_n, p.blue_n), N, ce_m ? "mixed-radix-registers" : axis_route(em, p.mix_m, p.blue_m),
-                 p.fold ? M / 2 : M, p.fold ? "x2" : "", p.tc, p.log_k, (long long)p.chunk, p.ws_bytes);
+                 p.fold ? M / 2 : M, p.fold ? "x2" : "", p.tc, p.log_k, (long long)p.chunk, p.ws_bytes, g);
     }
     return 0;
 }

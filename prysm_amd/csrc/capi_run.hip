@@ -16,8 +16,9 @@ static void set_input_mode(RowLoadNat<T>& lp, const pm_fft2_desc* d) {
     }
 }
 
+// the column store of the caller's output view; nt: streaming stores (the plan's nt_out)
 template <typename T>
-static ColStoreNat<T> make_colstore(const pm_fft2_desc* d, void* out, int logm_tile = -1) {
+static ColStoreNat<T> make_colstore(const pm_fft2_desc* d, void* out, int nt) {
     ColStoreNat<T> cs{};
     cs.dst = out;
     cs.ld = d->out_ld;
@@ -43,17 +44,7 @@ static ColStoreNat<T> make_colstore(const pm_fft2_desc* d, void* out, int logm_t
     if (d->epilogue != PM_EPI_NONE && (d->out_ld % 2 == 0) && (reinterpret_cast<uintptr_t>(out) % (2 * sizeof(T)) == 0) &&
         (d->out_bstride % 2 == 0))
         cs.vec_ok |= 2;
-    const size_t out_bytes = size_t(d->batch > 1 ? d->batch : 1) * size_t(d->out_y.len) * size_t(d->out_x.len) *
-                             (d->epilogue == PM_EPI_NONE ? sizeof(cx<T>) : sizeof(T));
-    // streaming stores only help when a workgroup writes whole 64 B pieces; on the 32 B pieces of 8192-point
-    // columns they defeat the L2 write combining of sibling workgroups (measured: 977 -> 428 us without)
-    if (logm_tile < 0) logm_tile = engine_log2(d->out_y.n) >= 0 ? engine_log2(d->out_y.n) : 12;
-    const size_t piece = size_t(col_tile_width_for(d->dtype, logm_tile, 0)) *
-                         (d->epilogue == PM_EPI_NONE ? sizeof(cx<T>) : sizeof(T));
-    // ... and only while the output is about the size of the 256 MiB Infinity Cache: measured +25 % at 256 MiB (4096^2
-    // complex128), -10 % at 512 MiB and 1 GiB (8192^2), -8 % at 128 MiB
-    cs.nt = tuning().nt_out >= 0 ? tuning().nt_out
-                                 : ((out_bytes >= (size_t(192) << 20) && out_bytes < (size_t(384) << 20) && piece >= 64) ? 1 : 0);
+    cs.nt = nt;
     return cs;
 }
 
@@ -82,56 +73,38 @@ static int fft2_run_chunk(const pm_fft2_desc* d, const Fft2Plan& p, const void* 
         const cx<T>* twn = twiddles<T>(N, &err);
         if (!twn) return err;
         const int64_t n2 = N / 2;
-        const int tc = col_tile_width_for(d->dtype, p.logm, 0);
-        const int ntiles = int((n2 + tc - 1) / tc);
+        const int tc = col_tile_width_for(d->dtype, p.fold ? p.logm - 1 : p.logm, 0);
+        const int tiles = int((n2 + tc - 1) / tc);
         const int64_t ld2 = d->in_ld / 2;
         ColLoadNat<T> cl{reinterpret_cast<const cx<T>*>(in), ld2, AxisMap{int(M), int(M), 0, 0}, int(n2), 0,
                          (ld2 % 2 == 0 && reinterpret_cast<uintptr_t>(in) % 16 == 0) ? 1 : 0, 0};
-        // fold (a radix-2 step of the column transform in the load, planes of M/2-point tiles: two workgroups per CU): from 4096 rows
-        const int hf = tuning().herm_t_fold;
-        const bool fold = (hf > 0 && p.logm >= 11) || (hf < 0 && p.logm >= 12);
-        HermTColStore<T> cs{W, N, int(n2), d->in_y.shift == M / 2 ? 1 : 0, fold ? 1 : 0, twm, 0};
-        const cx<T>* twa = twm;
-        int tiles = ntiles;
-        if (fold) {
-            twa = twiddles<T>(M / 2, &err);
-            if (!twa) return err;
-            const int tcf = col_tile_width_for(d->dtype, p.logm - 1, 0);
-            tiles = int((n2 + tcf - 1) / tcf);
-        }
-        cs.ntiles = tiles;
-        // adjacent tiles read the two halves of the input's 128 B lines and write adjacent lines of the intermediate: siblings on one XCD
-        // (profiles/r06/exp_herm_t_log_g.log, mtf_from_psf us at col_log_g 0 .. 5: 4096^2 fp32 folded 75.9 68.5 69.7 69.3 67.9 68.1 -- the pass reads
-        // 64 B pieces of a row-major array, neighbours share its 128 B lines --; 2048^2 (128 tiles, half the CUs) 31.9 33.6 33.7 33.8 34.2 34.4)
-        int lg = tuning().col_log_g >= 0 ? tuning().col_log_g : (p.logm >= 12 ? 4 : 0);
-        while (lg > 0 && ((fold ? 2 * tiles : tiles) % (8 << (lg + (fold ? 1 : 0)))) != 0) --lg;
-        int rc = launch_col_hermt<T>(p.logm, cl, cs, twa, tiles, lg, st);
+        // fold: the radix-2 step of the column transform in the load, planes of M/2-point tiles
+        HermTColStore<T> cs{W, N, int(n2), d->in_y.shift == M / 2 ? 1 : 0, p.fold ? 1 : 0, twm, tiles};
+        const cx<T>* twa = p.fold ? twiddles<T>(M / 2, &err) : twm;
+        if (!twa) return err;
+        int rc = launch_col_hermt<T>(p.logm, cl, cs, twa, tiles, p.col_log_g, st);
         if (rc) return rc < 0 ? fail(PM_ERR_UNSUPPORTED, "pm_fft2: internal: no transposed Hermitian column kernel for %lld points", (long long)M) : rc;
         // pass B: N-point transforms of the M/2 rows, each stored with its mirror image
         RowLoadNat<T> lp{W, N, AxisMap{int(N), int(N), 0, 0}, int(M / 2), 0, 0, 0};
         HermTRowStore<T> rs{out, d->out_ld, int(M), int(N), int(d->out_y.shift), int(d->out_x.shift), d->epilogue, T(d->scale),
                             (d->flags & PM_FLAG_NORM_DC) ? 1 : 0, W, d->in_x.shift == N / 2 ? 1 : 0, int(M / 2)};
-        rc = launch_row_hermt<T>(p.logn, tuning().herm_t_rowvar >= 0 ? tuning().herm_t_rowvar : row_variant(d->dtype, p.logn), lp, rs, twn, tuning().row_log_g, st);
+        rc = launch_row_hermt<T>(p.logn, p.row_var, lp, rs, twn, p.row_log_g, st);
         if (rc) return rc < 0 ? fail(PM_ERR_UNSUPPORTED, "pm_fft2: internal: no transposed Hermitian row kernel for %lld points", (long long)N) : rc;
         return 0;
     }
     if (p.r2c) {
         // rows: the real array read as N/2 complex points per row -> N/2 columns of the tiled intermediate (column 0 = X[0] + i X[N/2])
-        const int64_t n2 = N / 2, tl = int64_t(p.tc) << p.log_k;
-        int ltl = 0;
-        while ((int64_t(1) << ltl) < tl) ++ltl;
+        const int64_t n2 = N / 2, tl = int64_t(1) << p.ltl;
         const cx<T>* tw2 = twiddles<T>(n2, &err);
         if (!tw2) return err;
         const cx<T>* twn = twiddles<T>(N, &err);
         if (!twn) return err;
         const cx<T>* twm = twiddles<T>(M, &err);
         if (!twm) return err;
-        const size_t in_bytes = size_t(M) * size_t(N) * sizeof(T);
-        RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), d->in_ld / 2, AxisMap{int(n2), int(n2), 0, int(d->in_x.shift / 2)}, int(M), 0,
-                         tuning().nt_in >= 0 ? tuning().nt_in : (in_bytes >= (size_t(96) << 20) ? 1 : 0), 0};
+        RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), d->in_ld / 2, AxisMap{int(n2), int(n2), 0, int(d->in_x.shift / 2)}, int(M), 0, p.nt_in, 0};
         const int H = int(M / 2);
         const int64_t ntl = (n2 + tl - 1) / tl, plane = ntl * H * tl;
-        R2CRowStore<T> rs{W, int(M), ltl, twn, 0, 0, nullptr, 0};
+        R2CRowStore<T> rs{W, int(M), p.ltl, twn, 0, 0, nullptr, 0};
         if (p.fold) {
             lp.eoff = H;
             rs.nseq = H;
@@ -140,7 +113,7 @@ static int fft2_run_chunk(const pm_fft2_desc* d, const Fft2Plan& p, const void* 
             rs.twm = twm;
             rs.swap = d->in_y.shift == M / 2 ? 1 : 0;
         }
-        int rc = launch_row_r2c<T>(p.logn - 1, lp, rs, tw2, p.fold ? H : int(M), p.fold ? 0 : tuning().row_log_g, st);
+        int rc = launch_row_r2c<T>(p.logn - 1, lp, rs, tw2, p.fold ? H : int(M), p.row_log_g, st);
         if (rc) return rc < 0 ? fail(PM_ERR_UNSUPPORTED, "pm_fft2: internal: no Hermitian row kernel for %lld points", (long long)N) : rc;
         // columns: M-point transforms of the N/2 columns, each bin stored at (u, k) and conjugated at (-u, -k)
         const int ntiles = int((n2 + p.tc - 1) / p.tc);
@@ -155,17 +128,12 @@ static int fft2_run_chunk(const pm_fft2_desc* d, const Fft2Plan& p, const void* 
             ColLoadTiled<T> cl{W, H, AxisMap{H, H, 0, 0}, ntiles, p.log_k, plane};
             HermStore<T> hs{out, 2 * d->out_ld, AxisMap{H, H, 0, int(d->out_y.shift / 2)}, to_map(d->out_x), H, int(N), d->epilogue,
                             T(d->scale), T(d->weight), (d->flags & PM_FLAG_NORM_DC) ? 1 : 0, W, tl, H, 0, d->out_ld, fast, p.col_var == 2 ? 1 : 0};
-            // several rounds of one-workgroup-per-CU tiles (8192^2: 1024 of them): ALL 32 workgroups an XCD holds take adjacent tiles,
-            // so a row of the output is written 2 KiB at a time -- mtf_from_psf 8192^2 fp32 391 -> 373 us (exp_layout_sweep.log)
-            int lg = sibling_log_g(p.log_k);
-            if (tuning().col_log_g < 0 && 2 * ntiles > 2 * pm_num_cus())
-                for (lg = 5; lg > 3 && ntiles % (8 << lg); --lg) {}
-            return launch_col_herm<T>(p.logm - 1, cl, hs, twh, ntiles, lg, st);
+            return launch_col_herm<T>(p.logm - 1, cl, hs, twh, ntiles, p.col_log_g, st);
         }
         ColLoadTiled<T> cl{W, int(M), to_map(d->in_y), ntiles, p.log_k, 0};
         HermStore<T> hs{out, d->out_ld, to_map(d->out_y), to_map(d->out_x), int(M), int(N), d->epilogue, T(d->scale), T(d->weight),
                         (d->flags & PM_FLAG_NORM_DC) ? 1 : 0, W, tl, int(M), -1, 0, fast, p.col_var == 2 ? 1 : 0};
-        return launch_col_herm<T>(p.logm, cl, hs, twm, ntiles, sibling_log_g(p.log_k), st);
+        return launch_col_herm<T>(p.logm, cl, hs, twm, ntiles, p.col_log_g, st);
     }
 
     // ---- pass 1: one transform of length N per STORED input row (all-zero padded rows are skipped)
@@ -173,28 +141,22 @@ static int fft2_run_chunk(const pm_fft2_desc* d, const Fft2Plan& p, const void* 
         if (p.logn >= 0) {
             const cx<T>* tw = twiddles<T>(N, &err);
             if (!tw) return err;
-            const size_t in_bytes = size_t(p.nbatch) * size_t(rows) * size_t(d->in_x.len) * sizeof(cx<T>);
-            const int nt_in = tuning().nt_in >= 0 ? tuning().nt_in : (in_bytes >= (size_t(96) << 20) ? 1 : 0);
-            RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), d->in_ld, to_map(d->in_x), rows, conj, nt_in, d->in_bstride};
+            RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), d->in_ld, to_map(d->in_x), rows, conj, p.nt_in, d->in_bstride};
             set_input_mode(lp, d);
             int rc;
             if (p.fold) {
-                int ltc = 0;
-                while ((1 << ltc) < (p.tc << p.log_k)) ++ltc;
                 const cx<T>* twm = twiddles<T>(M, &err);
                 if (!twm) return err;
                 lp.eoff = int(M / 2);
-                const int64_t tl = int64_t(1) << ltc, ntl = (N + tl - 1) / tl;
-                RowStoreFold<T> sp{W, ntl * (M / 2) * tl, int(M / 2), ltc, twm, d->in_y.shift == M / 2 ? 1 : 0, 0};
-                rc = launch_row_fold<T>(p.logn, lp, sp, tw, int(M / 2), 0, st, 1);   // pairs are not siblings: no XCD grouping
+                const int64_t tl = int64_t(1) << p.ltl, ntl = (N + tl - 1) / tl;
+                RowStoreFold<T> sp{W, ntl * (M / 2) * tl, int(M / 2), p.ltl, twm, d->in_y.shift == M / 2 ? 1 : 0, 0};
+                rc = launch_row_fold<T>(p.logn, lp, sp, tw, int(M / 2), p.row_log_g, st, 1);
             } else if (p.tc) {
-                int ltc = 0;
-                while ((1 << ltc) < (p.tc << p.log_k)) ++ltc;
-                RowStoreTiled<T> sp{W, rows, ltc, wstride};
-                rc = launch_row_tiled<T>(p.logn, row_variant(d->dtype, p.logn), lp, sp, tw, rows, tuning().row_log_g, st, nb);
+                RowStoreTiled<T> sp{W, rows, p.ltl, wstride};
+                rc = launch_row_tiled<T>(p.logn, p.row_var, lp, sp, tw, rows, p.row_log_g, st, nb);
             } else {
                 RowStoreNat<T> sp{W, p.w_ld, AxisMap{int(N), int(N), 0, 0}, rows, 0, T(1), 0, AxisMap{1, 1, 0, 0}};
-                rc = launch_row_nat<T>(p.logn, row_variant(d->dtype, p.logn), lp, sp, tw, rows, 0, st);
+                rc = launch_row_nat<T>(p.logn, p.row_var, lp, sp, tw, rows, 0, st);
             }
             if (rc) return rc;
         } else {
@@ -237,7 +199,7 @@ static int fft2_run_chunk(const pm_fft2_desc* d, const Fft2Plan& p, const void* 
     if (!run2) return 0;
 
     // ---- pass 2: transforms of length M down the columns, epilogue fused into the store
-    ColStoreNat<T> cs = make_colstore<T>(d, out, p.fold ? p.logm - 1 : -1);
+    ColStoreNat<T> cs = make_colstore<T>(d, out, p.nt_out);
     if (p.fold) {
         // two planes of M/2-point column transforms: plane b holds output rows 2k + b -> output view with doubled
         // leading dimension, plane b offset by one row (the batch stride of the store)
@@ -250,7 +212,7 @@ static int fft2_run_chunk(const pm_fft2_desc* d, const Fft2Plan& p, const void* 
         cs.ay = AxisMap{H, int(d->out_y.len / 2), int(d->out_y.off / 2), int(d->out_y.shift / 2)};
         cs.bstride = d->out_ld;
         cs.ld = 2 * d->out_ld;
-        return launch_col_tiled<T>(p.logm - 1, p.col_var, cl, cs, tw, ntiles, sibling_log_g(p.log_k), st, 2);
+        return launch_col_tiled<T>(p.logm - 1, p.col_var, cl, cs, tw, ntiles, p.col_log_g, st, 2);
     }
     if (p.logm >= 0) {
         const cx<T>* tw = twiddles<T>(M, &err);
@@ -258,12 +220,12 @@ static int fft2_run_chunk(const pm_fft2_desc* d, const Fft2Plan& p, const void* 
         if (p.tc) {
             const int ntiles = int((N + p.tc - 1) / p.tc);
             ColLoadTiled<T> cl{W, rows, to_map(d->in_y), ntiles, p.log_k, wstride};
-            return launch_col_tiled<T>(p.logm, p.col_var, cl, cs, tw, ntiles, sibling_log_g(p.log_k), st, nb);
+            return launch_col_tiled<T>(p.logm, p.col_var, cl, cs, tw, ntiles, p.col_log_g, st, nb);
         }
         const int tc = col_tile_width_for(d->dtype, p.logm, 0);
         const int ntiles = int((N + tc - 1) / tc);
         ColLoadNat<T> cl{W, p.w_ld, to_map(d->in_y), int(N), 0, (p.w_ld % 2 == 0) ? 1 : 0};
-        return launch_col_nat<T>(p.logm, 0, cl, cs, tw, ntiles, 1, st);
+        return launch_col_nat<T>(p.logm, 0, cl, cs, tw, ntiles, p.col_log_g, st);
     }
     if (p.mix_m && p.mix_fold) {
         // two planes of M/2-point column transforms: plane b holds the output rows 2 k + b -- the output seen with a doubled leading
@@ -320,15 +282,6 @@ int fft2_run(const pm_fft2_desc* d, const Fft2Plan& p, const void* in, void* out
     return 0;
 }
 
-// Last row pass of the fused chains: streaming (non-temporal) stores -- the output is written once, in whole rows, and every line it does
-// not leave in the caches is a line of the intermediate that stays.  Measured (profiles/r03/exp_nt_rows.log, chain us without / with):
-// 4096^2 complex128 (256 MiB out) 344-347 / 320-321, padded 2048^2 -> 4096^2 complex128 343 / 326, 4096^2 complex64 (128 MiB) 167.7 /
-// 163.3, 2048^2 complex64 54.6 / 52.7, 2048^2 complex128 83.0 / 82.8.  Not beyond the Infinity Cache's size class (the two-pass
-// transform's column store lost 10 % with streaming stores at 512 MiB and 1 GiB, make_colstore).
-static int row_store_nt(size_t out_bytes) {
-    return tuning().nt_out >= 0 ? tuning().nt_out : ((out_bytes >= (size_t(24) << 20) && out_bytes < (size_t(384) << 20)) ? 1 : 0);
-}
-
 template <typename T>
 static int fused_run_chunk(const pm_fft2_desc* d, const FusedPlan& p, const void* in, void* out, void* ws, hipStream_t st, int nb) {
     const int64_t M = d->in_y.n, N = d->in_x.n;
@@ -342,9 +295,7 @@ static int fused_run_chunk(const pm_fft2_desc* d, const FusedPlan& p, const void
     if (!twN) return err;
     const cx<T>* twM = twiddles<T>(M, &err);
     if (!twM) return err;
-    const int tl = p.tc << p.log_k;
-    int ltl = 0;
-    while ((1 << ltl) < tl) ++ltl;
+    const int tl = 1 << p.ltl;
     if (p.fold) {
         // folded chain: row FFT + radix-2 DIF step -> two planes of M/2 rows; column FFT x H x IFFT per plane on M/2
         // points (in place); radix-2 DIT step + inverse row FFT -> natural output
@@ -352,12 +303,10 @@ static int fused_run_chunk(const pm_fft2_desc* d, const FusedPlan& p, const void
         const int64_t ntl = (N + tl - 1) / tl, plane = ntl * H * tl;
         const cx<T>* twH = twiddles<T>(H, &err);
         if (!twH) return err;
-        const size_t in_bytes = size_t(M) * size_t(d->in_x.len) * sizeof(cx<T>);
-        const int nt_in = tuning().nt_in >= 0 ? tuning().nt_in : (in_bytes >= (size_t(96) << 20) ? 1 : 0);
-        RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), d->in_ld, to_map(d->in_x), int(M), 0, nt_in, 0, 0, H};
+        RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), d->in_ld, to_map(d->in_x), int(M), 0, p.nt_in, 0, 0, H};
         set_input_mode(lp, d);
-        RowStoreFold<T> sp{W1, plane, H, ltl, twM, d->in_y.shift == M / 2 ? 1 : 0, 0};
-        int rc = launch_row_fold<T>(p.logn, lp, sp, twN, H, 0, st, 1);
+        RowStoreFold<T> sp{W1, plane, H, p.ltl, twM, d->in_y.shift == M / 2 ? 1 : 0, 0};
+        int rc = launch_row_fold<T>(p.logn, lp, sp, twN, H, p.row_log_g, st, 1);
         if (rc) return rc;
         const int ntiles = int((N + p.tc - 1) / p.tc);
         ColLoadTiled<T> cl{W1, H, AxisMap{H, H, 0, 0}, ntiles, p.log_k, plane};
@@ -366,21 +315,19 @@ static int fused_run_chunk(const pm_fft2_desc* d, const FusedPlan& p, const void
         mm.vec_ok = (d->mul_kind == PM_MUL_FULL && sizeof(T) == 4 && d->mul_ld % 2 == 0 &&
                      reinterpret_cast<uintptr_t>(d->mul) % 16 == 0) ? 1 : 0;
         ColStoreTiled<T> cst{W1, H, ntiles, p.log_k, plane};
-        rc = launch_col_mul<T>(p.logm - 1, cl, mm, cst, twH, ntiles, sibling_log_g(p.log_k), st, 2, tuning().colmul_mode);
+        rc = launch_col_mul<T>(p.logm - 1, cl, mm, cst, twH, ntiles, p.col_log_g, st, 2, p.colmul_mode);
         if (rc) return rc;
-        RowLoadFold<T> rl{W1, plane, H, ltl, twM, 1, 0};
+        RowLoadFold<T> rl{W1, plane, H, p.ltl, twM, 1, 0};
         RowStoreNat<T> rs{reinterpret_cast<cx<T>*>(out), d->out_ld, to_map(d->out_x), int(M), 1, T(d->scale), 1, to_map(d->out_y), 0, H};
-        rs.nt = row_store_nt(size_t(d->out_y.len) * size_t(d->out_x.len) * sizeof(cx<T>));
+        rs.nt = p.nt_out;
         return launch_row_unfold<T>(p.logn, rl, rs, twN, H, st, 1);
     }
     // pass A: forward row transforms of the stored input rows -> tiled W1
     if (rows > 0) {
-        const size_t in_bytes = size_t(p.nbatch) * size_t(rows) * size_t(d->in_x.len) * sizeof(cx<T>);
-        const int nt_in = tuning().nt_in >= 0 ? tuning().nt_in : (in_bytes >= (size_t(96) << 20) ? 1 : 0);
-        RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), d->in_ld, to_map(d->in_x), rows, 0, nt_in, d->in_bstride};
+        RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), d->in_ld, to_map(d->in_x), rows, 0, p.nt_in, d->in_bstride};
         set_input_mode(lp, d);
-        RowStoreTiled<T> sp{W1, rows, ltl, wstride};
-        int rc = launch_row_tiled<T>(p.logn, row_variant(d->dtype, p.logn), lp, sp, twN, rows, tuning().row_log_g, st, nb);
+        RowStoreTiled<T> sp{W1, rows, p.ltl, wstride};
+        int rc = launch_row_tiled<T>(p.logn, row_variant(d->dtype, p.logn), lp, sp, twN, rows, p.row_log_g, st, nb);
         if (rc) return rc;
     }
     // pass B: column FFT, x H, column IFFT (unnormalised) -> tiled W2 (all M rows)
@@ -391,7 +338,7 @@ static int fused_run_chunk(const pm_fft2_desc* d, const FusedPlan& p, const void
                  (d->mul_kind == PM_MUL_FULL && sizeof(T) == 4 && d->mul_ld % 2 == 0 && d->mul_bstride % 2 == 0 &&
                   reinterpret_cast<uintptr_t>(d->mul) % 16 == 0) ? 1 : 0};
     ColStoreTiled<T> cst{W2, int(M), ntiles, p.log_k, wstride};
-    int rc = launch_col_mul<T>(p.logm, cl, mm, cst, twM, ntiles, sibling_log_g(p.log_k), st, nb, tuning().colmul_mode);
+    int rc = launch_col_mul<T>(p.logm, cl, mm, cst, twM, ntiles, p.col_log_g, st, nb, p.colmul_mode);
     if (rc) return rc;
     // pass C: inverse row transforms of the rows inside the output window -> natural output, scale applied here.
     // Sequence s is stored row s of W2 (= logical row s); the output row map rotates / crops it.
@@ -403,9 +350,9 @@ static int fused_run_chunk(const pm_fft2_desc* d, const FusedPlan& p, const void
         nrun = int(d->out_y.len);
         oy = AxisMap{nrun, nrun, 0, 0};
     }
-    RowLoadTiled<T> rl{W2, int(M), ltl, row0, nrun, 1, wstride};
+    RowLoadTiled<T> rl{W2, int(M), p.ltl, row0, nrun, 1, wstride};
     RowStoreNat<T> rs{reinterpret_cast<cx<T>*>(out), d->out_ld, to_map(d->out_x), nrun, 1, T(d->scale), 1, oy, d->out_bstride};
-    rs.nt = row_store_nt(size_t(p.nbatch) * size_t(d->out_y.len) * size_t(d->out_x.len) * sizeof(cx<T>));
+    rs.nt = p.nt_out;
     return launch_row_from_tiled<T>(p.logn, row_variant(d->dtype, p.logn), rl, rs, twN, nrun, st, nb);
 }
 
@@ -437,7 +384,7 @@ static int fused_mix_run(const pm_fft2_desc* d, const FusedPlan& p, const void* 
         if (!twN) return err;
         RowLoadNat<T> lp{W2, p.w_ld, AxisMap{int(N), int(N), 0, 0}, int(M), 1, 0, 0};
         RowStoreNat<T> rs{reinterpret_cast<cx<T>*>(out), d->out_ld, to_map(d->out_x), int(M), 1, T(d->scale), 1, to_map(d->out_y), 0};
-        rs.nt = row_store_nt(size_t(d->out_y.len) * size_t(d->out_x.len) * sizeof(cx<T>));
+        rs.nt = p.nt_out;
         return launch_row_nat<T>(p.logn, row_variant(d->dtype, p.logn), lp, rs, twN, int(M), 0, st);
     }
     // the mixed-radix row kernel writes sequence s to memory row s: the kept positions [off, off + len) of the rotated rows are at most
@@ -455,7 +402,7 @@ static int fused_mix_run(const pm_fft2_desc* d, const FusedPlan& p, const void* 
 }
 
 template <typename T>
-static int blue2d_fused_run(const pm_fft2_desc* d, const void* in, void* out, void* ws, hipStream_t st);
+static int blue2d_fused_run(const pm_fft2_desc* d, const Fft2Plan& p, const void* in, void* out, void* ws, hipStream_t st);
 
 template <typename T>
 static int blue2d_run(const pm_fft2_desc* d, const Fft2Plan& p, const void* in, void* out, void* ws, hipStream_t st) {
@@ -470,7 +417,7 @@ static int blue2d_run(const pm_fft2_desc* d, const Fft2Plan& p, const void* in, 
     cx<T>* c = reinterpret_cast<cx<T>*>(static_cast<char*>(ws) + arr);
     void* fws = static_cast<char*>(ws) + 2 * arr;
     Blue2dIn<T> bi{in, d->in_ld, to_map(d->in_y), to_map(d->in_x), d->direction > 0 ? 1 : 0, (d->flags & PM_FLAG_REAL_INPUT) ? 1 : 0};
-    if (!p.blue_big && tuning().blue_fuse) return blue2d_fused_run<T>(d, in, out, fws, st);
+    if (p.blue_fuse) return blue2d_fused_run<T>(d, p, in, out, fws, st);
     int rc = blue_pre2d<T>(bi, a, t1, t2, st);
     if (rc) return rc;
     pm_fft2_desc dd;
@@ -501,14 +448,14 @@ static int blue2d_run(const pm_fft2_desc* d, const Fft2Plan& p, const void* in, 
         const Fft2Plan p2 = plan_fft2(&d2);
         if (!p2.big_rn) return fail(PM_ERR_UNSUPPORTED, "pm_fft2: internal: no big plan for the Bluestein convolution");
         if ((rc = big2d_run<T>(&d2, p2, S, c, bws, st))) return rc;
-        const ColStoreNat<T> cs = make_colstore<T>(d, out);
+        const ColStoreNat<T> cs = make_colstore<T>(d, out, p.nt_out);
         return blue_post2d<T>(c, int(M), int(N), t1, t2, cs, st);
     }
     FusedPlan fp;
     if (!plan_fused(&dd, fp)) return fail(PM_ERR_UNSUPPORTED, "pm_fft2: internal: no fused plan for the Bluestein convolution");
     rc = fused_run_chunk<T>(&dd, fp, a, c, fws, st, 1);
     if (rc) return rc;
-    const ColStoreNat<T> cs = make_colstore<T>(d, out);
+    const ColStoreNat<T> cs = make_colstore<T>(d, out, p.nt_out);
     return blue_post2d<T>(c, int(M), int(N), t1, t2, cs, st);
 }
 
@@ -516,7 +463,7 @@ static int blue2d_run(const pm_fft2_desc* d, const Fft2Plan& p, const void* in, 
 // w1 (x) w2 (RowLoadChirp), the last one stores conj(.) w1 (x) w2 through the caller's epilogue (RowStoreChirp).  Three launches,
 // no n1 x n2 temporaries.  (The unfolded passes of fused_run_chunk with those two ends.)
 template <typename T>
-static int blue2d_fused_run(const pm_fft2_desc* d, const void* in, void* out, void* ws, hipStream_t st) {
+static int blue2d_fused_run(const pm_fft2_desc* d, const Fft2Plan& p, const void* in, void* out, void* ws, hipStream_t st) {
     const int64_t n1 = d->in_y.n, n2 = d->in_x.n;
     int err = 0;
     const cx<T>* t1 = blue_tables<T>(n1, &err);
@@ -535,26 +482,23 @@ static int blue2d_fused_run(const pm_fft2_desc* d, const void* in, void* out, vo
     if (!twN) return err;
     const cx<T>* twM = twiddles<T>(M, &err);
     if (!twM) return err;
-    const int tl = fp.tc << fp.log_k;
-    int ltl = 0;
-    while ((1 << ltl) < tl) ++ltl;
     // pass A: rows x(i, .) w1[i] w2[.] padded to N, forward transform -> tiled W1 (n1 rows)
     RowLoadChirp<T> lp{Blue2dIn<T>{in, d->in_ld, to_map(d->in_y), to_map(d->in_x), d->direction > 0 ? 1 : 0,
                                    (d->flags & PM_FLAG_REAL_INPUT) ? 1 : 0},
                        t1, t2, rows};
-    RowStoreTiled<T> sp{W1, rows, ltl, 0};
-    int rc = launch_row_chirp_tiled<T>(fp.logn, row_variant(d->dtype, fp.logn), lp, sp, twN, rows, tuning().row_log_g, st);
+    RowStoreTiled<T> sp{W1, rows, fp.ltl, 0};
+    int rc = launch_row_chirp_tiled<T>(fp.logn, row_variant(d->dtype, fp.logn), lp, sp, twN, rows, fp.row_log_g, st);
     if (rc) return rc;
     // pass B: column FFT x (B1 (x) B2) x column IFFT -> tiled W2
     const int ntiles = int((N + fp.tc - 1) / fp.tc);
     ColLoadTiled<T> cl{W1, rows, AxisMap{int(M), rows, 0, 0}, ntiles, fp.log_k, 0};
     MidMul<T> mm{MUL_SEPARABLE, 0, t1 + n1, t2 + n2, 0, int(N), 0, 0, 0, 0};
     ColStoreTiledCrop<T> cst{W2, rows, ntiles, fp.log_k};   // only the n1 rows the crop keeps are stored
-    rc = launch_col_mul_crop<T>(fp.logm, cl, mm, cst, twM, ntiles, sibling_log_g(fp.log_k), st);
+    rc = launch_col_mul_crop<T>(fp.logm, cl, mm, cst, twM, ntiles, fp.col_log_g, st);
     if (rc) return rc;
     // pass C: inverse row transforms of the first n1 rows, bins [0, n2) x chirp through the caller's epilogue
-    RowLoadTiled<T> rl{W2, rows, ltl, 0, rows, 1, 0};
-    RowStoreChirp<T> rs{make_colstore<T>(d, out), t1, t2, int(n1), int(n2), 1};
+    RowLoadTiled<T> rl{W2, rows, fp.ltl, 0, rows, 1, 0};
+    RowStoreChirp<T> rs{make_colstore<T>(d, out, p.nt_out), t1, t2, int(n1), int(n2), 1};
     return launch_row_tiled_chirp<T>(fp.logn, row_variant(d->dtype, fp.logn), rl, rs, twN, rows, st);
 }
 
@@ -672,7 +616,7 @@ static int big2d_run(const pm_fft2_desc* d, const Fft2Plan& p, const void* in, v
         twM = twiddles<T>(M, &err);
         if (!twM) return err;
     }
-    ColStoreNat<T> ep = make_colstore<T>(d, out);
+    ColStoreNat<T> ep = make_colstore<T>(d, out, p.nt_out);
     ep.bstride = 0;
     return big_finish<T>(F, mp, np, Rm, Rn, twM, ep, st);
 }
@@ -843,12 +787,10 @@ int herm_conv_run(const pm_fft2_desc* d, const HermConvPlan& p, const void* in, 
     if (!twn) return err;
     const cx<T>* twm = twiddles<T>(M, &err);
     if (!twm) return err;
-    const int64_t tl = int64_t(p.tc) << p.log_k;
-    int ltl = 0;
-    while ((int64_t(1) << ltl) < tl) ++ltl;
+    const int64_t tl = int64_t(1) << p.ltl;
     // rows: the real array as N/2 complex points per row -> N/2 columns, column 0 = X[0] + i X[N/2]
     RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), d->in_ld / 2, AxisMap{int(n2), int(n2), 0, int(d->in_x.shift / 2)}, int(M), 0, 0, 0};
-    R2CRowStore<T> rs{W, int(M), ltl, twn, 0, 0, nullptr, 0};
+    R2CRowStore<T> rs{W, int(M), p.ltl, twn, 0, 0, nullptr, 0};
     if (p.fold) {
         // folded: two planes of M/2 rows (even / odd bins of the column transform), M/2-point column tiles, the last pass rebuilds row pairs
         const int H = int(M / 2);
@@ -861,35 +803,35 @@ int herm_conv_run(const pm_fft2_desc* d, const HermConvPlan& p, const void* in, 
         rs.plane_stride = plane;
         rs.twm = twm;
         rs.swap = d->in_y.shift == M / 2 ? 1 : 0;
-        int rcf = launch_row_r2c<T>(p.logn - 1, lp, rs, tw2, H, 0, st);
+        int rcf = launch_row_r2c<T>(p.logn - 1, lp, rs, tw2, H, p.row_log_g, st);
         if (rcf) return rcf < 0 ? fail(PM_ERR_UNSUPPORTED, "pm_fft2_mul_ifft2: internal: no folded Hermitian row kernel for %lld points", (long long)N) : rcf;
         const int ntf = int(n2 / p.tc);
         ColLoadTiled<T> clf{W, H, AxisMap{H, H, 0, 0}, ntf, p.log_k, plane};
         HermMul<T> hmf{reinterpret_cast<const cx<T>*>(d->mul), d->mul_ld, int(M), int(N), d->mul_conj ? 1 : 0, 1};
         ColStoreTiled<T> csf{W, H, ntf, p.log_k, plane};
-        rcf = launch_col_mul_herm<T>(p.logm - 1, clf, hmf, csf, twh, ntf, sibling_log_g(p.log_k), st);
+        rcf = launch_col_mul_herm<T>(p.logm - 1, clf, hmf, csf, twh, ntf, p.col_log_g, st);
         if (rcf) return rcf < 0 ? fail(PM_ERR_UNSUPPORTED, "pm_fft2_mul_ifft2: internal: no Hermitian column kernel for %lld points", (long long)H) : rcf;
-        RowLoadFold<T> rlf{W, plane, H, ltl, twm, 0, 0};
+        RowLoadFold<T> rlf{W, plane, H, p.ltl, twm, 0, 0};
         RowStoreNat<T> rof{reinterpret_cast<cx<T>*>(out), d->out_ld / 2, AxisMap{int(n2), int(n2), 0, int(d->out_x.shift / 2)}, int(M), 1,
                            T(d->scale), 1, to_map(d->out_y), 0, H};
-        rof.nt = row_store_nt(size_t(M) * size_t(N) * sizeof(T));
+        rof.nt = p.nt_out;
         rcf = launch_row_c2r_fold<T>(p.logn - 1, rlf, rof, tw2, twn, H, st);
         return rcf < 0 ? fail(PM_ERR_UNSUPPORTED, "pm_fft2_mul_ifft2: internal: no folded half-spectrum row kernel for %lld points", (long long)N) : rcf;
     }
-    int rc = launch_row_r2c<T>(p.logn - 1, lp, rs, tw2, int(M), tuning().row_log_g, st);
+    int rc = launch_row_r2c<T>(p.logn - 1, lp, rs, tw2, int(M), p.row_log_g, st);
     if (rc) return rc < 0 ? fail(PM_ERR_UNSUPPORTED, "pm_fft2_mul_ifft2: internal: no Hermitian row kernel for %lld points", (long long)N) : rc;
     // columns: transform, x the Hermitian part of H, inverse transform, in place
     const int ntiles = int(n2 / p.tc);
     ColLoadTiled<T> cl{W, int(M), to_map(d->in_y), ntiles, p.log_k, 0};
     HermMul<T> hm{reinterpret_cast<const cx<T>*>(d->mul), d->mul_ld, int(M), int(N), d->mul_conj ? 1 : 0, 0};
     ColStoreTiled<T> cst{W, int(M), ntiles, p.log_k, 0};
-    rc = launch_col_mul_herm<T>(p.logm, cl, hm, cst, twm, ntiles, sibling_log_g(p.log_k), st);
+    rc = launch_col_mul_herm<T>(p.logm, cl, hm, cst, twm, ntiles, p.col_log_g, st);
     if (rc) return rc < 0 ? fail(PM_ERR_UNSUPPORTED, "pm_fft2_mul_ifft2: internal: no Hermitian column kernel for %lld points", (long long)M) : rc;
     // rows back: half spectra -> N real samples per row = N/2 complex elements of the output seen as complex
-    RowLoadTiled<T> rl{W, int(M), ltl, 0, int(M), 0, 0};
+    RowLoadTiled<T> rl{W, int(M), p.ltl, 0, int(M), 0, 0};
     RowStoreNat<T> ro{reinterpret_cast<cx<T>*>(out), d->out_ld / 2, AxisMap{int(n2), int(n2), 0, int(d->out_x.shift / 2)}, int(M), 1,
                       T(d->scale), 1, to_map(d->out_y), 0, 0};
-    ro.nt = row_store_nt(size_t(M) * size_t(N) * sizeof(T));
+    ro.nt = p.nt_out;
     rc = launch_row_c2r<T>(p.logn - 1, rl, ro, tw2, twn, int(M), st);
     return rc < 0 ? fail(PM_ERR_UNSUPPORTED, "pm_fft2_mul_ifft2: internal: no half-spectrum row kernel for %lld points", (long long)N) : rc;
 }
@@ -902,13 +844,9 @@ int fft2_spectral_group(const pm_fft2_desc* d, const Fft2Plan& p, const Spectral
     cx<T>* W = reinterpret_cast<cx<T>*>(ws);
     const cx<T>* tw = twiddles<T>(N, &err);
     if (!tw) return err;
-    const size_t in_bytes = size_t(rows) * size_t(d->in_x.len) * sizeof(cx<T>);
-    const int nt_in = tuning().nt_in >= 0 ? tuning().nt_in : (in_bytes >= (size_t(96) << 20) ? 1 : 0);
-    RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), d->in_ld, to_map(d->in_x), rows, 0, nt_in, 0};
-    int ltc = 0;
-    while ((1 << ltc) < (p.tc << p.log_k)) ++ltc;
-    const int64_t tl = int64_t(1) << ltc, ntl = (N + tl - 1) / tl;
-    ColStoreNat<T> cs = make_colstore<T>(d, out, p.fold ? p.logm - 1 : -1);
+    RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), d->in_ld, to_map(d->in_x), rows, 0, p.nt_in, 0};
+    const int64_t tl = int64_t(1) << p.ltl, ntl = (N + tl - 1) / tl;
+    ColStoreNat<T> cs = make_colstore<T>(d, out, p.nt_out);
     const int ntiles = int((N + p.tc - 1) / p.tc);
     int rc;
     if (p.fold) {
@@ -918,20 +856,20 @@ int fft2_spectral_group(const pm_fft2_desc* d, const Fft2Plan& p, const Spectral
         const cx<T>* twh = twiddles<T>(H, &err);
         if (!twh) return err;
         lp.eoff = H;
-        RowStoreFold<T> sp{W, ntl * H * tl, H, ltc, twm, d->in_y.shift == M / 2 ? 1 : 0, 0};
+        RowStoreFold<T> sp{W, ntl * H * tl, H, p.ltl, twm, d->in_y.shift == M / 2 ? 1 : 0, 0};
         if ((rc = launch_row_spectral_fold<T>(p.logn, lp, sp, tw, H, w, st))) return rc;
         ColLoadTiled<T> cl{W, H, AxisMap{H, H, 0, 0}, ntiles, p.log_k, ntl * H * tl};
         cs.ay = AxisMap{H, int(d->out_y.len / 2), int(d->out_y.off / 2), int(d->out_y.shift / 2)};
         cs.bstride = d->out_ld;
         cs.ld = 2 * d->out_ld;
-        return launch_col_spectral<T>(p.logm - 1, cl, cs, twh, ntiles, sibling_log_g(p.log_k), w, st, 2);
+        return launch_col_spectral<T>(p.logm - 1, cl, cs, twh, ntiles, p.col_log_g, w, st, 2);
     }
     const cx<T>* twm = twiddles<T>(M, &err);
     if (!twm) return err;
-    RowStoreTiled<T> sp{W, rows, ltc, 0};
-    if ((rc = launch_row_spectral<T>(p.logn, row_variant(d->dtype, p.logn), lp, sp, tw, rows, tuning().row_log_g, w, st))) return rc;
+    RowStoreTiled<T> sp{W, rows, p.ltl, 0};
+    if ((rc = launch_row_spectral<T>(p.logn, p.row_var, lp, sp, tw, rows, p.row_log_g, w, st))) return rc;
     ColLoadTiled<T> cl{W, rows, to_map(d->in_y), ntiles, p.log_k, 0};
-    return launch_col_spectral<T>(p.logm, cl, cs, twm, ntiles, sibling_log_g(p.log_k), w, st, 1);
+    return launch_col_spectral<T>(p.logm, cl, cs, twm, ntiles, p.col_log_g, w, st, 1);
 }
 
 // the runners the entry points call (capi.hip), both precisions

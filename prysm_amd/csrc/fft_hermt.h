@@ -285,12 +285,16 @@ __global__ void __launch_bounds__(C::NT, MINW) fft_row_hermt_kernel(const RowLoa
 }
 
 // ---------------------------------------------------------------- launchers (instantiated in fft_hermt_f32.hip / fft_hermt_f64.hip)
+template <typename T>
+constexpr int hermt_dtype = sizeof(T) == 4 ? PM_C64 : PM_C128;
+
 template <typename T, int LOGM, bool FOLD>
 int launch_col_hermt_one(const ColLoadNat<T>& lp, const HermTColStore<T>& sp, const cx<T>* tw, int ntiles, int log_g, hipStream_t st) {
-    using C = typename ColCfgSel<T, FOLD ? LOGM - 1 : LOGM, 0>::type;
-    if constexpr (FOLD && C::BO != 1) {
+    if constexpr (!hermt_col_kernel(hermt_dtype<T>, LOGM, FOLD)) {
         return -2;
     } else {
+        using C = typename ColCfgSel<T, FOLD ? LOGM - 1 : LOGM, 0>::type;
+        static_assert(!FOLD || C::BO == 1, "the folded column kernel takes one tile per workgroup");
         auto kern = fft_col_hermt_kernel<C, FOLD>;
         constexpr size_t LDSB = C::LDS_BYTES;
         if (LDSB > 48 * 1024) {
@@ -304,25 +308,15 @@ int launch_col_hermt_one(const ColLoadNat<T>& lp, const HermTColStore<T>& sp, co
     }
 }
 
-// tw: the table of the transform the kernel runs -- M points, or M / 2 with sp.fold (sp.twm is then the M-point table)
+// tw: the table of the transform the kernel runs -- M points, or M / 2 with sp.fold (sp.twm is then the M-point table).  Every engine
+// length is a case; which of them has a kernel is hermt_col_kernel's alone.
 template <typename T>
 int launch_col_hermt_impl(int logm, const ColLoadNat<T>& lp, const HermTColStore<T>& sp, const cx<T>* tw, int ntiles, int log_g, hipStream_t st) {
-    if (sp.fold) {
-        switch (logm) {
-#define PM_CASE(k) \
-    case k:        \
-        return launch_col_hermt_one<T, k, true>(lp, sp, tw, ntiles, log_g, st);
-            PM_CASE(10) PM_CASE(11) PM_CASE(12) PM_CASE(13)
-#undef PM_CASE
-            default:
-                return -2;
-        }
-    }
     switch (logm) {
 #define PM_CASE(k) \
     case k:        \
-        return launch_col_hermt_one<T, k, false>(lp, sp, tw, ntiles, log_g, st);
-        PM_CASE(5) PM_CASE(6) PM_CASE(7) PM_CASE(8) PM_CASE(9) PM_CASE(10) PM_CASE(11) PM_CASE(12)
+        return sp.fold ? launch_col_hermt_one<T, k, true>(lp, sp, tw, ntiles, log_g, st) : launch_col_hermt_one<T, k, false>(lp, sp, tw, ntiles, log_g, st);
+        PM_CASE(5) PM_CASE(6) PM_CASE(7) PM_CASE(8) PM_CASE(9) PM_CASE(10) PM_CASE(11) PM_CASE(12) PM_CASE(13)
 #undef PM_CASE
         default:
             return -2;
@@ -349,7 +343,8 @@ int launch_row_hermt_epi(const RowLoadNat<T>& lp, const HermTRowStore<T>& sp, co
 
 template <typename T, int LOGN, int VAR>
 int launch_row_hermt_one(const RowLoadNat<T>& lp, const HermTRowStore<T>& sp, const cx<T>* tw, int log_g, hipStream_t st) {
-    switch (sp.epilogue) {
+    if constexpr (!hermt_row_kernel(hermt_dtype<T>, LOGN)) return -2;
+    else switch (sp.epilogue) {
         case EPI_NONE: return launch_row_hermt_epi<T, LOGN, VAR, EPI_NONE>(lp, sp, tw, log_g, st);
         case EPI_ABS2: return launch_row_hermt_epi<T, LOGN, VAR, EPI_ABS2>(lp, sp, tw, log_g, st);
         case EPI_ABS: return launch_row_hermt_epi<T, LOGN, VAR, EPI_ABS>(lp, sp, tw, log_g, st);
@@ -358,7 +353,8 @@ int launch_row_hermt_one(const RowLoadNat<T>& lp, const HermTRowStore<T>& sp, co
     }
 }
 
-// one tiling per length and precision, the complex path's (pm_internal.h row_variant): `var` only tells 2048-point rows apart
+// one tiling per length and precision, the complex path's (pm_internal.h row_variant): `var` only tells 4096-point complex64 rows apart;
+// which lengths have a kernel is hermt_row_kernel's alone
 template <typename T>
 int launch_row_hermt_impl(int logn, int var, const RowLoadNat<T>& lp, const HermTRowStore<T>& sp, const cx<T>* tw, int log_g, hipStream_t st) {
     switch (logn) {
@@ -374,8 +370,7 @@ int launch_row_hermt_impl(int logn, int var, const RowLoadNat<T>& lp, const Herm
             if constexpr (sizeof(T) == 4) return var == 0 ? launch_row_hermt_one<T, 12, 0>(lp, sp, tw, log_g, st) : launch_row_hermt_one<T, 12, 4>(lp, sp, tw, log_g, st);
             else return launch_row_hermt_one<T, 12, 0>(lp, sp, tw, log_g, st);
         case 13:
-            if constexpr (sizeof(T) == 4) return launch_row_hermt_one<T, 13, 4>(lp, sp, tw, log_g, st);
-            else return -2;
+            return launch_row_hermt_one<T, 13, 4>(lp, sp, tw, log_g, st);
         default:
             return -2;
     }

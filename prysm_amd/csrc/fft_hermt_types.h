@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fft_io.h"
+#include "prysm_amd.h"
 #include "fft_r2c_types.h"
 
 namespace pm {
@@ -36,6 +37,12 @@ struct HermTRowStore {
     int neg_odd;        // the input columns came rotated by N/2: bins of odd k change sign
     int nseq;           // M / 2 rows
 };
+
+// The kernels that exist (launch_col_hermt_one / launch_row_hermt_one launch exactly these; capi_plan.hip hermt_legal plans by them):
+// columns of 32 .. 4096 points, or with the fold 2048 .. 8192 as two planes of half-length tiles (from 1024-point tiles, where ColCfgSel
+// gives one tile per workgroup); rows of 32 .. 4096 points, 8192 for complex64.  dtype: PM_C64 / PM_C128.
+constexpr bool hermt_col_kernel(int dtype, int logm, bool fold) { return fold ? (logm >= 11 && logm <= 13) : (logm >= 5 && logm <= 12); }
+constexpr bool hermt_row_kernel(int dtype, int logn) { return logn >= 5 && logn <= (dtype == PM_C64 ? 13 : 12); }
 
 template <typename T> int launch_col_hermt(int logm, const ColLoadNat<T>&, const HermTColStore<T>&, const cx<T>* tw, int ntiles, int log_g, hipStream_t);
 template <typename T> int launch_row_hermt(int logn, int var, const RowLoadNat<T>&, const HermTRowStore<T>&, const cx<T>* tw, int log_g, hipStream_t);

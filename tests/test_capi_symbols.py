@@ -330,3 +330,66 @@ def test_routes_follow_the_knobs_and_tuning_local_nests(lib):
     with L.tuning_local(mix_engine=0):      # round 5: composite lengths with a compile-time plan back on the general kernel
         assert 'rows=mixed-radix(3000)' in _route(lib, 3000, 3000)
     assert 'rows=mixed-radix-registers(3000)' in _route(lib, 3000, 3000)
+
+
+# The transposed-Hermitian kernels that are built (fft_hermt_types.h hermt_col_kernel / hermt_row_kernel): columns of 32 .. 4096 points,
+# or folded 2048 .. 8192; rows of 32 .. 4096 points, 8192 for complex64
+def _hermt_col_kernel(logm, fold):
+    return 11 <= logm <= 13 if fold else 5 <= logm <= 12
+
+
+def _hermt_row_kernel(dt, logn):
+    return 5 <= logn <= (13 if dt == 'c64' else 12)
+
+
+def test_transposed_hermitian_plans_only_kernels_that_exist(lib):
+    """Whatever the fold knob, a shape the planner sends down the transposed Hermitian form has both its kernels, for the fold the
+    planner reports, and a workspace"""
+    from prysm_amd import _lib as L
+    seen = 0
+    for hf in (-1, 0, 1):
+        with L.tuning_local(herm_t=1, herm_t_fold=hf):
+            for dt in ('c64', 'c128'):
+                for logm in range(5, 14):
+                    for logn in range(5, 14):
+                        m, n = 1 << logm, 1 << logn
+                        try:
+                            line = _route(lib, m, n, dt=dt, real=True, epi=L.PM_EPI_ABS)
+                        except NotImplementedError:       # no Hermitian path at all (complex128 rows of 8192 samples)
+                            assert dt == 'c128' and logn == 13
+                            continue
+                        if 'route=hermitian-transposed' not in line:
+                            continue
+                        seen += 1
+                        fold = line.endswith(' fold')
+                        assert _hermt_col_kernel(logm, fold) and _hermt_row_kernel(dt, logn), (hf, line)
+                        assert fold == (logm >= 11 if hf > 0 else logm >= 12 if hf < 0 else False), (hf, line)
+                        d = L.pm_fft2_desc()
+                        d.dtype, d.direction, d.flags, d.epilogue = (L.PM_C64 if dt == 'c64' else L.PM_C128), -1, L.PM_FLAG_REAL_INPUT, L.PM_EPI_ABS
+                        d.in_y, d.in_x, d.in_ld = L.pm_axis(m, m, 0, m // 2), L.pm_axis(n, n, 0, n // 2), n
+                        d.out_y, d.out_x, d.out_ld = L.pm_axis(m, m, 0, m // 2), L.pm_axis(n, n, 0, n // 2), n
+                        assert lib.pm_fft2_workspace(ctypes.byref(d)) > 0, line
+    assert seen > 200
+
+
+def test_explain_shows_the_launch_choices_the_plan_makes(lib):
+    """The fold of the transposed Hermitian form and the column sibling groups are the planner's (the runner reads them from the plan)"""
+    from prysm_amd import _lib as L
+    mtf = dict(real=True, epi=L.PM_EPI_ABS)
+    assert _route(lib, 4096, 4096, **mtf).endswith('route=hermitian-transposed cols=stockham-r2c(4096) rows=stockham(4096)x2048 ws=67108864 g=4 fold')
+    line = _route(lib, 2048, 2048, **mtf)
+    assert 'route=hermitian-transposed' in line and 'fold' not in line and line.endswith(' g=0'), line
+    assert 'g=4 fold' in _route(lib, 8192, 2048, **mtf)
+    assert _route(lib, 8192, 8192, **mtf).endswith('route=hermitian-fold rows=stockham-r2c(4096) cols=stockham(4096x2) tile=8 log_k=3 ws=268435456 g=5')
+    assert _route(lib, 4096, 4096).endswith('log_k=7 chunk=1 ws=134217728 g=3')
+    assert _route(lib, 1024, 1024).endswith(' g=1') and _route(lib, 8192, 8192).endswith(' g=3')
+    assert ' g=' not in _route(lib, 3000, 3000)
+    with L.tuning_local(herm_t_fold=0):
+        assert _route(lib, 4096, 4096, **mtf).endswith('ws=67108864 g=4')
+    with L.tuning_local(herm_t_fold=1):
+        assert _route(lib, 2048, 2048, **mtf).endswith(' fold')
+    with L.tuning_local(col_log_g=2):
+        assert _route(lib, 4096, 4096, **mtf).endswith(' g=2 fold')
+        assert _route(lib, 4096, 4096).endswith(' g=2') and _route(lib, 8192, 8192, **mtf).endswith(' g=2')
+    with L.tuning_local(col_log_g=7):     # the sibling group of the tiled column pass stops at 2^5
+        assert _route(lib, 4096, 4096).endswith(' g=5')
