@@ -315,6 +315,35 @@ int pm_sample_spline(int32_t dtype, int32_t order, int64_t map_rows, int64_t map
                      int64_t xf_sx, const void* yf, int64_t yf_sy, int64_t yf_sx, const void* fill, int64_t fill_ld,
                      double fill_re, double fill_im, void* out, int64_t out_ld, void* stream);
 
+/* --- deformable mirror (prysm/x/dm.py) ------------------------------------------------------ */
+enum { PM_LATTICE_SCATTER = 0, PM_LATTICE_GATHER = 1 };
+
+/* The actuator lattice of x.dm.DM (prepare_actuator_lattice, prysm/x/dm.py:18-61; geometry is the caller's) for a stack of `batch`
+ * fields, lattice point (i, j) at grid sample (y0 + i sy, x0 + j sx):
+ *   PM_LATTICE_SCATTER: out (rows x cols, REAL) = 0 everywhere, scale * in[i][j] at the lattice points -- the poke array of DM.render
+ *                       (`poke_arr[iyy, ixx] = actuators`, dm.py:247); in is nact_y x nact_x.  dtype PM_F32 or PM_F64.
+ *   PM_LATTICE_GATHER:  out (nact_y x nact_x, REAL) = scale * in at the lattice points -- `in_actuator_space[iyy, ixx]` of
+ *                       DM.render_adjoint (dm.py:331); in is rows x cols, REAL (PM_F32 / PM_F64) or, with PM_C64 / PM_C128, the real
+ *                       part of a complex array (in_ld and in_bstride in complex elements).
+ * A lattice that does not fit inside the grid, or strides that make outputs overlap, are PM_ERR_ARG. */
+int pm_lattice(int32_t dtype, int32_t op, int64_t batch, int64_t rows, int64_t cols, int64_t nact_y, int64_t nact_x, int64_t y0,
+               int64_t x0, int64_t sy, int64_t sx, double scale, const void* in, int64_t in_ld, int64_t in_bstride, void* out,
+               int64_t out_ld, int64_t out_bstride, void* stream);
+
+/* Pull-warp of a REAL (batch, rows, cols) stack by a 3 x 3 homography H (row-major, 9 HOST doubles, passed to the kernels by value):
+ * coordinates.warp (prysm/coordinates.py:644-672) at apply_homography's points (coordinates.py:545-570) as DM.render / render_adjoint
+ * call it (dm.py:256, 326), i.e. for warp pixel (R, C):  (x', y', w) = H (C, R, 1);  value = scale * map_coordinates(img, (y'/w, x'/w),
+ * order=3, mode='constant', cval=0), coordinates in fp64.  A coordinate outside [0, n - 1] on either axis gives exactly 0; inside, the
+ * cubic B-spline of the mirror-prefiltered image.  The result goes through an output window: out (out_rows x out_cols) pixel (r, c) is
+ * warp pixel (r + off_y, c + off_x), 0 outside the rows x cols warp domain (pad2d / crop_center, dm.py:267-271).  dtype PM_F32 /
+ * PM_F64, or PM_C64 / PM_C128 to warp the real part of a complex stack (in_ld, in_bstride in complex elements); out is REAL.
+ * order: 3 only (PM_ERR_UNSUPPORTED otherwise).  Two launches: the prefilter (a separable FIR of 2K + 1 taps, K = 30 fp64 / 14 fp32,
+ * the exact impulse response of scipy's recursion) into the workspace, then the 4 x 4 tap evaluation. */
+size_t pm_warp_workspace(int32_t dtype, int64_t batch, int64_t rows, int64_t cols);
+int pm_warp(int32_t dtype, int32_t order, int64_t batch, int64_t rows, int64_t cols, const void* in, int64_t in_ld, int64_t in_bstride,
+            const double* homography, double scale, int64_t out_rows, int64_t out_cols, int64_t off_y, int64_t off_x, void* out,
+            int64_t out_ld, int64_t out_bstride, void* workspace, size_t workspace_bytes, void* stream);
+
 /* P = amp * exp(i * k * opd), k = 2 pi / (wavelength_um * 1e3) for opd in nm.
  * amp may be NULL (unit amplitude: phase_screen).  amp_dtype in {PM_F32, PM_F64, PM_BOOL}.
  * Wavefront.from_amp_and_phase / phase_screen (wavefront.py:58-96), phase_prefix (_kernels.py:40-43). */
