@@ -344,6 +344,38 @@ int pm_warp(int32_t dtype, int32_t order, int64_t batch, int64_t rows, int64_t c
             const double* homography, double scale, int64_t out_rows, int64_t out_cols, int64_t off_y, int64_t off_x, void* out,
             int64_t out_ld, int64_t out_bstride, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Zernike polynomials without a stored basis (csrc/zernike.hip).  Points are npts contiguous REAL values per coordinate (dtype PM_F32 /
+ * PM_F64, computed in that precision): coords PM_ZERNIKE_CARTESIAN reads (u, v) = (x, y), PM_ZERNIKE_POLAR reads (u, v) = (r, t).
+ * `table` is a DEVICE array of nsteps steps built by prysm_amd/polynomials/zernike_plan.py (struct pm::ZStep: T a, b, c, w;
+ * int32 op, part, slot, dm -- 32 bytes for PM_F32, 48 for PM_F64): modes sorted by |m| then Jacobi order, each step a Jacobi
+ * recurrence step (DLMF 18.9, alpha = 0, beta = |m|) on 2 r^2 - 1, z^|m| (z = x + i y) advanced at each new |m|, and the output slot
+ * in [0, nmodes), norm factor and cos / sin part of the mode written there.  Z_n^m = w P_{(n-|m|)//2}^(0,|m|)(2 r^2 - 1) {1, Re z^|m|,
+ * Im z^|m|} is the reference's zernike_nm (prysm/polynomials/zernike.py:34-69) with r^|m| cos(m t) = Re z^|m|. */
+enum { PM_ZERNIKE_CARTESIAN = 0, PM_ZERNIKE_POLAR = 1 };
+
+/* out (nmodes, npts): every mode of the table, one launch -- zernike_nm_seq / zernike_nm (zernike.py:72-163, 34-69). */
+int pm_zernike_basis(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
+                     int64_t nmodes, void* out, void* stream);
+
+/* out[b][p] (+)= sum_k coefs[b][k] Z_k[p] for batch coefficient vectors (coefs: DEVICE, batch x nmodes, read at launch time, so a
+ * captured graph uses their current values); out is batch x npts, added to when accumulate != 0.  zernike_sum (zernike.py:166-181)
+ * without materialising zernike_nm_seq; one walk of the table per point for each group of up to 8 vectors. */
+int pm_zernike_sum(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
+                   int64_t nmodes, int64_t batch, const void* coefs, int32_t accumulate, void* out, void* stream);
+
+/* out[b][k] = sum_p databar[b][p] Z_k[p] (databar batch x npts, out batch x nmodes): the adjoint of pm_zernike_sum with respect to the
+ * coefficients, i.e. sum_of_2d_modes_adjoint(zernike_nm_seq(...), databar) (fitting.py:40-57) without the basis.  Two launches: one
+ * partial per (workgroup, b, k) into the workspace, then a fixed-order sum of the partials -- no atomics, bitwise reproducible. */
+size_t pm_zernike_project_workspace(int32_t dtype, int64_t npts, int64_t nmodes, int64_t batch);
+int pm_zernike_project(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
+                       int64_t nmodes, int64_t batch, const void* databar, void* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* out[k] = sum_p modes[k * mode_stride + p] v[p], k < nmodes, p < npts: np.tensordot(modes, databar) of sum_of_2d_modes_adjoint
+ * (fitting.py:40-57).  REAL PM_F32 / PM_F64; two launches, deterministic as pm_zernike_project. */
+size_t pm_modes_dot_workspace(int32_t dtype, int64_t nmodes, int64_t npts);
+int pm_modes_dot(int32_t dtype, int64_t nmodes, int64_t npts, const void* modes, int64_t mode_stride, const void* v, void* out, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 /* P = amp * exp(i * k * opd), k = 2 pi / (wavelength_um * 1e3) for opd in nm.
  * amp may be NULL (unit amplitude: phase_screen).  amp_dtype in {PM_F32, PM_F64, PM_BOOL}.
  * Wavefront.from_amp_and_phase / phase_screen (wavefront.py:58-96), phase_prefix (_kernels.py:40-43). */
