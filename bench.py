@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: pupil -> focus FFT propagations per second at 4096^2 complex64.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 N > 1 runs N ranks, one process per GPU, over RCCL (torch.distributed backend "nccl").  Either the caller launches
 them (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py
@@ -14,7 +14,11 @@ A "step" is ONE propagation ``focus(x, Q=1)`` = fftshift(fft2(ifftshift(x), norm
 shards over wavelengths / fields with no data-path collective (weak scaling): every rank propagates its own field, the
 timed region is exactly K propagations per rank between barrier + synchronize pairs, MAX over ranks.
 
-After the timed region, outside of it and on every rank:
+A plain run does only what the headline needs: set-up, the run-in and W warm-up steps, the K timed steps, --dump-outputs, and rank
+0's ONE JSON line (metric, value, unit, ms_per_step, dtype, ..., the run-in and the device's clocks around the timed region).
+Everything else below is measured with ``--full`` only.
+
+With --full, after the timed region, outside of it and on every rank:
 * ``n2048``: the same measurement at 2048^2 (the second size the north star names);
 * ``polychromatic``: BASELINE config 5 as ONE timed call of prysm_amd.polychromatic.polychromatic_psf -- 64
   wavelengths x 4096^2 fp32 sharded over the N ranks, |.|^2 accumulated per rank, one sum-reduce of the image to rank 0
@@ -27,7 +31,8 @@ After the timed region, outside of it and on every rank:
 The headline line is complete before any of that starts; if the side measurements hang (their collectives meet RCCL on
 an N > 1 node for the first time in the driver's runs) a watchdog prints it without them after --extras-budget seconds.
 
-Rank 0 prints ONE JSON line.  ``roofline``: the dominant kernel (the slower of the two FFT passes), its duration
+With --full the line also carries ``repeat_ms``: four more batches of K steps timed like the headline, right after it, and
+``roofline``: the dominant kernel (the slower of the two FFT passes), its duration
 measured with HIP events recorded between the kernels on the launch stream, in sequence; achieved = 2 N^2 s
 algorithmic bytes (read + write of one pass) / duration, peak 8 TB/s; ``traffic`` = PMC bytes per launch from the
 committed rocprofv3 summary, printed only while the kernel sources still hash to the fingerprint the summary was
@@ -138,15 +143,19 @@ def parse():
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--edge', dest='n', type=int, default=N_EDGE, help='transform edge (default 4096, the headline); not --n: torch.distributed.run would read that as an abbreviation of its own options')
     ap.add_argument('--dtype', default='c64', choices=['c64', 'c128'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-poly', action='store_true', help='only the headline loop (profiling runs)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, every side measurement: repeat batches, roofline, 2048^2, config 5, the other configs, '
+                         'the CPU baseline (a plain run times the headline only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-poly', action='store_true', help='with --full: skip 2048^2, the intensity variant, config 5 and the other configs')
     ap.add_argument('--only', default='', help='profiling runs: time only this other_configs entry (model7|config2|config3|config4|c128|n8192|padded|composite|mtf|conv|adjoint|poly2048)')
-    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='budget for the CPU baseline sample')
+    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='--full: budget for the CPU baseline sample')
     ap.add_argument('--reduce-method', default='auto', choices=['auto', 'reduce', 'a2a', 'rs'],
                     help='how the polychromatic image reaches rank 0: one torch.distributed.reduce, or all-to-all of slices + ordered local '
                          'sum + gather (one message per xGMI link); auto = whichever reduces the 67 MB image faster in this run')
-    ap.add_argument('--extras-budget', type=float, default=900.0,
-                    help='seconds the side measurements after the timed region may take before the headline line is printed without them')
+    ap.add_argument('--extras-budget', type=float, default=480.0,
+                    help='--full: seconds the side measurements after the timed region may take before the headline line is printed without '
+                         'them (the default keeps a --full run within 10 minutes)')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='torch.distributed backend (nccl = RCCL; gloo only to exercise the N > 1 path when the ranks share a GPU)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -292,6 +301,27 @@ def pmc_traffic(kernel, n, dtype_name):
             if k.startswith(want) and k.endswith(f'_{real}_N{nn}'):
                 return v['hbm_traffic_bytes'], f'profiles/pmc_bench_summary.json:{k} (source fingerprint {stamp})'
     return None, 'kernel not in the PMC summary'
+
+
+def roofline(x, n, ms_step, dtype_name):
+    """--full: the dominant pass of the headline step against the HBM roofline, and two plain copies of the same field."""
+    es = x.element_size()
+    p1, p2 = kernel_pass_times(x, n)
+    two_copies_ms = plain_copy_pair_ms(x)
+    dom, dom_ms = ('row_pass', p1) if p1 >= p2 else ('column_pass', p2)
+    alg_bytes_kernel = 2.0 * n * n * es           # one pass reads N^2 s and writes N^2 s
+    achieved = alg_bytes_kernel / (dom_ms * 1e-3) / 1e9
+    traffic, traffic_src = pmc_traffic(dom, n, dtype_name)
+    return {'bound': 'hbm', 'kernel': dom, 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+            'frac': achieved / HBM_PEAK_GBS, 'frac_of_measured_copy_ceiling': achieved / HBM_COPY_CEILING_GBS,
+            'traffic': traffic, 'traffic_unit': 'bytes per launch',
+            'traffic_source': traffic_src, 'algorithmic_bytes_per_launch': alg_bytes_kernel,
+            'row_pass_ms': p1, 'column_pass_ms': p2, 'passes_over_step': (p1 + p2) / ms_step,
+            'two_plain_copies_ms': two_copies_ms, 'step_over_two_plain_copies': ms_step / two_copies_ms,
+            'note': '2*N^2*s algorithmic bytes per pass / average HIP-event duration of that pass, each pass timed as its own '
+                    'back-to-back loop of 100 launches on the launch stream (pm_fft2_time_passes); passes_over_step = '
+                    '(row + column) / ms_per_step; two_plain_copies_ms = torch copies in -> ws -> out of the same field, '
+                    'measured in this run'}
 
 
 SIDE_PREWARM_MS = 100.0    # untimed run-in of every side measurement (the headline loop has its own, PREWARM_MIN_MS): they follow each other with
@@ -1148,7 +1178,6 @@ def main():
         else:
             dist.init_process_group('gloo')
     ranks = Ranks(world)
-    from prysm_amd import propagation as P
 
     n = args.n
     cdtype = np.complex64 if args.dtype == 'c64' else np.complex128
@@ -1166,7 +1195,7 @@ def main():
     if world > 1:
         dist.all_reduce(torch.zeros(1, device='cuda'))     # create the communicator outside every timed region
     loop_info = {}
-    elapsed, f = propagation_loop(ranks, x, args.steps, args.warmup, info=loop_info, repeats=4)
+    elapsed, f = propagation_loop(ranks, x, args.steps, args.warmup, info=loop_info, repeats=4 if args.full else 0)
     dumped = dump_outputs(f, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     del f
 
@@ -1175,13 +1204,7 @@ def main():
     if rank == 0:
         ms_step = elapsed / args.steps * 1e3
         value = world * args.steps / elapsed
-        p1, p2 = kernel_pass_times(x, n)
-        two_copies_ms = plain_copy_pair_ms(x)
-        dom, dom_ms = ('row_pass', p1) if p1 >= p2 else ('column_pass', p2)
-        alg_bytes_kernel = 2.0 * n * n * es           # one pass reads N^2 s and writes N^2 s
-        achieved = alg_bytes_kernel / (dom_ms * 1e-3) / 1e9
         alg_bytes_step = 4.0 * n * n * es             # 4 N^2 s per propagation
-        traffic, traffic_src = pmc_traffic(dom, n, args.dtype)
         line = {
             'metric': 'pupil->focus FFT propagations per second (PSFs/s), 4096^2',
             'value': value, 'unit': 'propagations/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -1191,21 +1214,14 @@ def main():
                                    '(fftshift(fft2(ifftshift(x), norm=ortho)), complex field out)',
                        'fields_per_gpu_per_step': 1, 'parallelism': f'one field/wavelength per GPU x{world}',
                        'backend': ('RCCL (torch.distributed nccl)' if args.backend == 'nccl' else 'gloo') if world > 1 else 'none',
-                       'reduce': 'none in the timed region (independent fields); the polychromatic sum-reduce is timed in `polychromatic`'},
+                       'reduce': 'none in the timed region (independent fields); the polychromatic sum-reduce is timed in `polychromatic` '
+                                 '(--full)'},
             'whole_step_algorithmic_GBps_per_gpu': alg_bytes_step / (ms_step * 1e-3) / 1e9,
             'whole_step_frac_of_hbm_peak': alg_bytes_step / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
             'whole_step_frac_of_measured_copy_ceiling': alg_bytes_step / (ms_step * 1e-3) / 1e9 / HBM_COPY_CEILING_GBS,
-            'roofline': {'bound': 'hbm', 'kernel': dom, 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': achieved / HBM_PEAK_GBS, 'frac_of_measured_copy_ceiling': achieved / HBM_COPY_CEILING_GBS,
-                         'traffic': traffic, 'traffic_unit': 'bytes per launch',
-                         'traffic_source': traffic_src, 'algorithmic_bytes_per_launch': alg_bytes_kernel,
-                         'row_pass_ms': p1, 'column_pass_ms': p2, 'passes_over_step': (p1 + p2) / ms_step,
-                         'two_plain_copies_ms': two_copies_ms, 'step_over_two_plain_copies': ms_step / two_copies_ms,
-                         'note': '2*N^2*s algorithmic bytes per pass / average HIP-event duration of that pass, each pass timed as its own '
-                                 'back-to-back loop of 100 launches on the launch stream (pm_fft2_time_passes); passes_over_step = '
-                                 '(row + column) / ms_per_step; two_plain_copies_ms = torch copies in -> ws -> out of the same field, '
-                                 'measured in this run'},
         }
+        if args.full:
+            line['roofline'] = roofline(x, n, ms_step, args.dtype)
         line.update(loop_info)
         if dumped:
             line['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
@@ -1214,6 +1230,20 @@ def main():
             allr = rep + [ms_step]
             line['repeat_spread'] = (max(allr) - min(allr)) / min(allr)
 
+    if args.full:
+        side_measurements(args, ranks, rank, x, cdtype, line)
+    elif rank == 0:
+        emit(line)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def side_measurements(args, ranks, rank, x, cdtype, line):
+    """--full: everything after the headline (the module docstring lists it); rank 0 prints the line, `line` (None on the other
+    ranks) with them."""
+    from prysm_amd import propagation as P
+    world, n = ranks.world, args.n
     # The side measurements below include this code's collectives (config 5).  A hang or a crash there must not cost the run its
     # headline: after --extras-budget seconds rank 0 prints the line it already has and every rank leaves (one JSON line either way).
     printed = threading.Event()
@@ -1284,9 +1314,6 @@ def main():
             printed.set()
             emit(line)
     dog.cancel()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == '__main__':

@@ -77,7 +77,7 @@ def test_bench_two_ranks_selflaunch(pa):
     timed config-5 run."""
     be = _two_rank_backend()
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2', '--edge', '1024',
-           '--no-cpu-baseline', '--backend', be]
+           '--full', '--no-cpu-baseline', '--backend', be]
     env = _env()
     env.pop('WORLD_SIZE', None)
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
@@ -90,6 +90,27 @@ def test_bench_two_ranks_selflaunch(pa):
     assert poly['wavelengths_per_gpu'] == 32
     assert poly['variant_F_fft_focus']['psf_ms'] > 0 and poly['variant_M_mdft_512']['psf_ms'] > 0
     assert line['n2048']['value'] > 0 and line['reduce_ms'] > 0
+
+
+def test_bench_plain_run_is_the_headline_only(pa, tmp_path):
+    """`python bench.py` without --full: ONE line with the headline keys and the dumped focal field of the last timed step, and none
+    of the side measurements --full adds"""
+    import bench
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '5', '--warmup', '2', '--edge', '1024', '--dump-outputs', str(tmp_path)]
+    res = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, res.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line['unit'] == 'propagations/s' and line['higher_is_better'] is True and line['dtype'] == 'c64' and line['steps'] == 5
+    assert line['value'] > 0 and abs(line['value'] * line['ms_per_step'] / 1e3 - 1) < 1e-5
+    for key in ('roofline', 'repeat_ms', 'n2048', 'polychromatic', 'polychromatic_2048', 'psf_variant', 'other_configs', 'cpu_baseline'):
+        assert key not in line, key
+    assert line['dumped_outputs']['arrays'] == {'focus': {'shape': [1024, 1024, 2], 'dtype': 'float32'}}
+    got = np.load(tmp_path / 'focus.npy')
+    x = bench.make_field(1024, np.complex64, 4096)
+    want = tonp(pa.propagation.focus(x, 1))
+    assert rel_max(got[..., 0] + 1j * got[..., 1], want) < TOL32
 
 
 def test_polychromatic_two_ranks_vs_oracle(pa):

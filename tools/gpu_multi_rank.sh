@@ -7,7 +7,7 @@
 R=${GRAFT_REPO_ROOT:-$PWD}; O=${1:-$R/gpurun_out/multi_rank}; mkdir -p $O
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 # (1) the bench itself, launched the way a user would: python bench.py --gpus 2 (self_launch -> torch.distributed.run)
-( timeout 900 python $R/bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --backend gloo ) > $O/bench_2rank_gloo.log 2>&1
+( timeout 900 python $R/bench.py --gpus 2 --steps 20 --warmup 5 --full --no-cpu-baseline --backend gloo ) > $O/bench_2rank_gloo.log 2>&1
 grep '"metric"' $O/bench_2rank_gloo.log | tail -1 > $O/bench_2rank_gloo.json
 # (2) the sharded driver against the oracle, 2 ranks
 ( timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 \
