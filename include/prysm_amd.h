@@ -376,6 +376,39 @@ size_t pm_modes_dot_workspace(int32_t dtype, int64_t nmodes, int64_t npts);
 int pm_modes_dot(int32_t dtype, int64_t nmodes, int64_t npts, const void* modes, int64_t mode_stride, const void* v, void* out, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* Segmented apertures (csrc/segmented.hip): CompositeHexagonalAperture.compose_opd (prysm/segmented.py:178-285) and its adjoint.
+ * The grid is rows x cols REAL points (dtype PM_F32 / PM_F64, computed in that precision); x, y are the aperture's DEVICE coordinate
+ * arrays.  `plan` is a DEVICE array of nseg 80-byte segment records built by prysm_amd/segmented.py (struct pm::SegDesc: int32 y0, x0,
+ * h, w -- the segment's window; int32 gy0, gx0 and 2 pad -- the window of its grid source, whose local coordinates it uses; int64 moff
+ * -- its mask in `masks`, h x w values; int64 boff -- the (nmodes, h, w) stored basis of its grid source in `basis`; double cx, cy --
+ * the grid source's centre; double nr -- the normalisation radius; double pad).  Z_{s,k} comes from `source`: PM_SEGMENT_ZERNIKE walks
+ * the Zernike step `table` (as pm_zernike_sum, Cartesian) at ((x - cx) / nr, (y - cy) / nr) of the grid source, at the same position
+ * in its window; PM_SEGMENT_STORED reads basis[boff + k h w + position].  Check a plan with pm_segment_plan_check before it is used. */
+enum { PM_SEGMENT_ZERNIKE = 0, PM_SEGMENT_STORED = 1 };
+
+/* Host-side check of a HOST copy of `plan`: every window and grid-source window inside the grid, every mask inside mask_elems and,
+ * for basis_elems >= 0, every stored basis of nmodes planes inside basis_elems; nr > 0.  0, or PM_ERR_ARG with pm_last_error(). */
+int pm_segment_plan_check(int64_t rows, int64_t cols, int64_t nseg, const void* plan, int64_t mask_elems, int64_t nmodes,
+                          int64_t basis_elems);
+
+/* out[b][p] (+)= sum over the segments s of p's cover list of mask_s[p] * sum_k coefs[b][s][k] Z_{s,k}[p] -- compose_opd
+ * (segmented.py:261-285) with the segments' windows added in segment order.  cover: ncover DEVICE int16 planes of rows x cols, plane
+ * i holding the i-th segment (index into plan) whose window covers the point with a non-zero mask, -1 after the last; points of no
+ * segment keep out (accumulate != 0) or get 0.  coefs: DEVICE, batch x nseg x nmodes, read at launch time (a captured graph uses their
+ * current values).  One launch per group of up to 8 coefficient stacks. */
+int pm_segment_compose(int32_t dtype, int32_t source, int64_t rows, int64_t cols, const void* x, const void* y, int64_t nseg, const void* plan,
+                       const void* masks, int64_t ncover, const void* cover, const void* table, int64_t nsteps, int64_t nmodes,
+                       const void* basis, int64_t batch, const void* coefs, int32_t accumulate, void* out, void* stream);
+
+/* out[b][s][k] = sum over the window of s of mask_s[p] Z_{s,k}[p] databar[b][p] (databar batch x rows x cols, out batch x nseg x
+ * nmodes): the adjoint of pm_segment_compose with respect to the coefficients; the reference has none (prepare_opd_bases /
+ * compose_opd, segmented.py:178-285).  window_pts: the largest h * w of the plan.  Two launches: one partial per (workgroup, b, s, k)
+ * into the workspace, each workgroup on one segment, then a fixed-order sum -- no atomics, bitwise reproducible. */
+size_t pm_segment_project_workspace(int32_t dtype, int64_t window_pts, int64_t nseg, int64_t nmodes, int64_t batch);
+int pm_segment_project(int32_t dtype, int32_t source, int64_t rows, int64_t cols, const void* x, const void* y, int64_t nseg, const void* plan,
+                       const void* masks, int64_t window_pts, const void* table, int64_t nsteps, int64_t nmodes, const void* basis,
+                       int64_t batch, const void* databar, void* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* P = amp * exp(i * k * opd), k = 2 pi / (wavelength_um * 1e3) for opd in nm.
  * amp may be NULL (unit amplitude: phase_screen).  amp_dtype in {PM_F32, PM_F64, PM_BOOL}.
  * Wavefront.from_amp_and_phase / phase_screen (wavefront.py:58-96), phase_prefix (_kernels.py:40-43). */
