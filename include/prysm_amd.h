@@ -352,6 +352,9 @@ int pm_warp(int32_t dtype, int32_t order, int64_t batch, int64_t rows, int64_t c
  * in [0, nmodes), norm factor and cos / sin part of the mode written there.  Z_n^m = w P_{(n-|m|)//2}^(0,|m|)(2 r^2 - 1) {1, Re z^|m|,
  * Im z^|m|} is the reference's zernike_nm (prysm/polynomials/zernike.py:34-69) with r^|m| cos(m t) = Re z^|m|. */
 enum { PM_ZERNIKE_CARTESIAN = 0, PM_ZERNIKE_POLAR = 1 };
+/* Radial points for the Q-polynomial walk (pm_qpoly_*): u only, v is not read and may be NULL (angle 0).  The Zernike entry points
+ * refuse it. */
+enum { PM_QPOLY_RADIAL = 2 };
 
 /* out (nmodes, npts): every mode of the table, one launch -- zernike_nm_seq / zernike_nm (zernike.py:72-163, 34-69). */
 int pm_zernike_basis(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
@@ -375,6 +378,32 @@ int pm_zernike_project(int32_t dtype, int32_t coords, int64_t npts, const void* 
 size_t pm_modes_dot_workspace(int32_t dtype, int64_t nmodes, int64_t npts);
 int pm_modes_dot(int32_t dtype, int64_t nmodes, int64_t npts, const void* modes, int64_t mode_stride, const void* v, void* out, void* workspace,
                  size_t workspace_bytes, void* stream);
+
+/* Forbes Q polynomials without a stored basis (csrc/qpoly.hip): Qbfs, Qcon and Q2D (prysm/polynomials/qpoly.py).  Points as for the
+ * Zernike walk, plus coords PM_QPOLY_RADIAL (u only).  `table` is a DEVICE array of nsteps steps built by
+ * prysm_amd/polynomials/qpoly_plan.py (struct pm::QStep: T a, b, c, d, g, h, rf, w; int32 op, part, slot, dm -- 48 bytes for PM_F32,
+ * 80 for PM_F64): modes grouped by |m|, one step per order n.  With x = u^2 each step, by its op bits, may RESET the group (z^|m| *= z
+ * dm times, P = Q = 0), SEED the auxiliary polynomial (P_{n-1} = P, P = a + b x + c x^2 + d x^3) or ADVance it (P_n = (a + b x) P_{n-1}
+ * - c P_{n-2}); either of the last two is followed by the Q step Q_n = (P_n - g Q_{n-1} - h Q_{n-2}) * rf.  A step whose part is not
+ * NONE (0) writes w Q_n times x (1 - x) (1, Qbfs), x^2 (2, Qcon), Re z^|m| (3) or Im z^|m| (4) into plane slot; a slot outside
+ * [0, nmodes) writes nothing.  Replaces the reference's per-mode numpy loops: Qbfs (qpoly.py:65), Qbfs_seq (408), Qcon (621),
+ * Qcon_seq (654), Q2d (893), Q2d_seq (1003), and the sums compute_z_Qbfs (349) and compute_z_Q2d (1888). */
+
+/* out (nmodes, npts): every mode of the table, one launch -- Qbfs_seq, Qcon_seq, Q2d_seq and their single-mode forms. */
+int pm_qpoly_basis(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
+                   int64_t nmodes, void* out, void* stream);
+
+/* out[b][p] (+)= sum_k coefs[b][k] Q_k[p] for batch coefficient vectors (coefs: DEVICE, batch x nmodes, read at launch time);
+ * out is batch x npts, added to when accumulate != 0.  compute_z_Qbfs / compute_z_Q2d (qpoly.py:349, 1888) and the package's
+ * Q2d_sum / Qcon_sum without the basis; one walk of the table per point for each group of up to 8 vectors. */
+int pm_qpoly_sum(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
+                 int64_t nmodes, int64_t batch, const void* coefs, int32_t accumulate, void* out, void* stream);
+
+/* out[b][k] = sum_p databar[b][p] Q_k[p]: the adjoint of pm_qpoly_sum with respect to the coefficients (the reference has none).  Two
+ * launches as pm_zernike_project: per-workgroup partials into the workspace, then a fixed-order sum -- bitwise reproducible. */
+size_t pm_qpoly_project_workspace(int32_t dtype, int64_t npts, int64_t nmodes, int64_t batch);
+int pm_qpoly_project(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
+                     int64_t nmodes, int64_t batch, const void* databar, void* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Segmented apertures (csrc/segmented.hip): CompositeHexagonalAperture.compose_opd (prysm/segmented.py:178-285) and its adjoint.
  * The grid is rows x cols REAL points (dtype PM_F32 / PM_F64, computed in that precision); x, y are the aperture's DEVICE coordinate

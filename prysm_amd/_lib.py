@@ -24,6 +24,7 @@ PM_FLAG_REAL_OUTPUT = 64
 PM_ERR_ARG, PM_ERR_UNSUPPORTED, PM_ERR_WORKSPACE = -1, -2, -3
 PM_LATTICE_SCATTER, PM_LATTICE_GATHER = 0, 1
 PM_ZERNIKE_CARTESIAN, PM_ZERNIKE_POLAR = 0, 1
+PM_QPOLY_RADIAL = 2
 PM_SEGMENT_ZERNIKE, PM_SEGMENT_STORED = 0, 1
 
 c_i32, c_i64, c_f64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
@@ -101,6 +102,10 @@ SIGNATURES = {
     'pm_zernike_project': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'pm_modes_dot_workspace': (c_sz, [c_i32, c_i64, c_i64]),
     'pm_modes_dot': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'pm_qpoly_basis': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    'pm_qpoly_sum': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp]),
+    'pm_qpoly_project_workspace': (c_sz, [c_i32, c_i64, c_i64, c_i64]),
+    'pm_qpoly_project': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'pm_segment_plan_check': (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64]),
     'pm_segment_compose': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                    c_vp, c_i32, c_vp, c_vp]),

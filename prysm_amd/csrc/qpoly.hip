@@ -1,0 +1,394 @@
+// Forbes Q polynomials without a stored basis (prysm/polynomials/qpoly.py: Qbfs, Qcon, Q2D) (gfx950):
+//
+//  - pm_qpoly_basis: the K planes of Qbfs_seq / Qcon_seq / Q2d_seq, one launch.
+//  - pm_qpoly_sum: sum_k c[b][k] Q_k for B coefficient vectors (Q2d_sum, Qcon_sum, compute_z_Qbfs, compute_z_Q2d), the basis
+//    evaluated once per point per group of up to 8 vectors and never stored.
+//  - pm_qpoly_project: sum_p g[b][p] Q_k[p] (the adjoint of pm_qpoly_sum with respect to c), same walk.
+//
+// Every point walks one table of steps built on the host (prysm_amd/polynomials/qpoly_plan.py): modes grouped by |m|, one step per
+// order n.  The auxiliary polynomial P (a three-term recurrence in x = u^2, or a cubic seed), the orthogonalised Q (Q_n = (P_n -
+// g Q_{n-1} - h Q_{n-2}) / f) and z^|m| (z = x + i y) stay in registers, so u^|m| cos(|m| t) = Re z^|m| and u^|m| sin(|m| t) =
+// Im z^|m| need no trigonometry in the loop.  Radial tables (Qbfs, Qcon) take PM_QPOLY_RADIAL points: u only, no angle read.  The
+// step index is uniform, so the table is read through the scalar cache.  A step whose slot is outside [0, nmodes) writes nothing.
+//
+// The tile, its 16-byte loads and stores, the wave reduction and the fixed-order second stage are zernike_walk.h's; the projection is
+// pm_zernike_project's scheme: per-workgroup partials in the caller's workspace, then a fixed-order sum.  No atomics, so every run and
+// every graph replay gives the same bits.
+#include "zernike_walk.h"
+
+#define PM_STREAM(s) reinterpret_cast<hipStream_t>(s)
+
+namespace pm {
+namespace {
+
+constexpr int kMaxProjectGroups = 1024;                 // workgroups of a projection (grid-stride beyond): the partial count per output
+constexpr size_t kProjectLds = 64 * 1024;               // per-wave accumulators of a projection workgroup
+
+enum { QS_RESET = 1, QS_SEED = 2, QS_ADV = 4 };
+enum { QP_NONE = 0, QP_BFS = 1, QP_CON = 2, QP_COS = 3, QP_SIN = 4 };
+
+// one step of the table (qpoly_plan.step_dtype)
+template <typename T>
+struct QStep {
+    T a, b, c, d, g, h, rf, w;
+    int32_t op, part, slot, dm;
+};
+static_assert(sizeof(QStep<float>) == 48 && sizeof(QStep<double>) == 80, "QStep layout is shared with qpoly_plan.step_dtype");
+
+// The walk of the step table over kVec points, E steps at a time: emit(j, slot, values) at the j-th step of a group that writes, then
+// flush() after every group of E steps.  coords: PM_ZERNIKE_CARTESIAN (u, v) = (x, y), PM_ZERNIKE_POLAR (r, t), PM_QPOLY_RADIAL u
+// only (z = u, angle 0).
+template <int E, typename T, typename Emit, typename Flush>
+__device__ __forceinline__ void qwalk(int coords, const T u[kVec], const T v[kVec], const QStep<T>* __restrict__ table, int nsteps, int nmodes,
+                                      Emit&& emit, Flush&& flush) {
+    T X[kVec], zx[kVec], zy[kVec], pr[kVec], pi[kVec], p[kVec], pm[kVec], q1[kVec], q2[kVec];
+#pragma unroll
+    for (int q = 0; q < kVec; ++q) {
+        if (coords == PM_ZERNIKE_POLAR) {
+            T s, c;
+            sincos_(v[q], &s, &c);
+            zx[q] = u[q] * c;
+            zy[q] = u[q] * s;
+            X[q] = u[q] * u[q];
+        } else if (coords == PM_ZERNIKE_CARTESIAN) {
+            zx[q] = u[q];
+            zy[q] = v[q];
+            X[q] = u[q] * u[q] + v[q] * v[q];
+        } else {
+            zx[q] = u[q];
+            zy[q] = T(0);
+            X[q] = u[q] * u[q];
+        }
+        pr[q] = T(1);
+        pi[q] = T(0);
+        p[q] = pm[q] = q1[q] = q2[q] = T(0);
+    }
+    for (int s0 = 0; s0 < nsteps; s0 += E) {
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            if (s0 + j >= nsteps) break;
+            const QStep<T> st = table[s0 + j];
+            if (st.op & QS_RESET) {
+                for (int d = 0; d < st.dm; ++d) {
+#pragma unroll
+                    for (int q = 0; q < kVec; ++q) {
+                        const T r = pr[q] * zx[q] - pi[q] * zy[q];
+                        pi[q] = pr[q] * zy[q] + pi[q] * zx[q];
+                        pr[q] = r;
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < kVec; ++q) p[q] = pm[q] = q1[q] = q2[q] = T(0);
+            }
+            if (st.op & QS_SEED) {
+#pragma unroll
+                for (int q = 0; q < kVec; ++q) {
+                    pm[q] = p[q];
+                    p[q] = st.a + X[q] * (st.b + X[q] * (st.c + X[q] * st.d));
+                }
+            } else if (st.op & QS_ADV) {
+#pragma unroll
+                for (int q = 0; q < kVec; ++q) {
+                    const T n = (st.a + st.b * X[q]) * p[q] - st.c * pm[q];
+                    pm[q] = p[q];
+                    p[q] = n;
+                }
+            }
+            if (st.op & (QS_SEED | QS_ADV)) {
+#pragma unroll
+                for (int q = 0; q < kVec; ++q) {
+                    const T n = (p[q] - st.g * q1[q] - st.h * q2[q]) * st.rf;
+                    q2[q] = q1[q];
+                    q1[q] = n;
+                }
+            }
+            if (st.part != QP_NONE && unsigned(st.slot) < unsigned(nmodes)) {
+                T z[kVec];
+#pragma unroll
+                for (int q = 0; q < kVec; ++q) {
+                    const T wq = st.w * q1[q];
+                    const T pre = st.part == QP_BFS ? X[q] * (T(1) - X[q])
+                                  : st.part == QP_CON ? X[q] * X[q]
+                                  : st.part == QP_COS ? pr[q] : pi[q];
+                    z[q] = wq * pre;
+                }
+                emit(j, st.slot, z);
+            }
+        }
+        flush();
+    }
+}
+
+// the coordinates of the lane's points: v is not read for radial points
+template <typename T>
+__device__ __forceinline__ void load_coords(int coords, const T* __restrict__ u, const T* __restrict__ v, int64_t base, int lane, int64_t npts,
+                                            bool full, T uu[kVec], T vv[kVec]) {
+    load_pts(u, base, lane, npts, full, uu);
+    if (coords != PM_QPOLY_RADIAL)
+        load_pts(v, base, lane, npts, full, vv);
+    else
+#pragma unroll
+        for (int q = 0; q < kVec; ++q) vv[q] = T(0);
+}
+
+// ---------------------------------------------------------------- basis: K planes, write-bound
+template <typename T>
+__global__ __launch_bounds__(kThreads) void qpoly_basis_kernel(int64_t npts, int coords, const T* __restrict__ u, const T* __restrict__ v,
+                                                               const QStep<T>* __restrict__ table, int nsteps, int nmodes, T* __restrict__ out,
+                                                               int vec) {
+    const int lane = threadIdx.x & 63;
+    const int64_t base = wave_tile(threadIdx.x >> 6);
+    if (base >= npts) return;
+    const bool full = vec && base + 64 * kVec <= npts;
+    T uu[kVec], vv[kVec];
+    load_coords(coords, u, v, base, lane, npts, full, uu, vv);
+    qwalk<1>(coords, uu, vv, table, nsteps, nmodes,
+             [&](int, int k, const T z[kVec]) { store_pts<true>(out + int64_t(k) * npts, base, lane, npts, full, z); }, [] {});
+}
+
+// ---------------------------------------------------------------- sum: NB coefficient vectors per walk
+template <typename T, int NB>
+__global__ __launch_bounds__(kThreads) void qpoly_sum_kernel(int64_t npts, int coords, const T* __restrict__ u, const T* __restrict__ v,
+                                                             const QStep<T>* __restrict__ table, int nsteps, int nmodes,
+                                                             const T* __restrict__ coefs, int accumulate, T* __restrict__ out, int vec) {
+    const int lane = threadIdx.x & 63;
+    const int64_t base = wave_tile(threadIdx.x >> 6);
+    if (base >= npts) return;
+    const bool full = vec && base + 64 * kVec <= npts;
+    T uu[kVec], vv[kVec], acc[NB][kVec];
+    load_coords(coords, u, v, base, lane, npts, full, uu, vv);
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int q = 0; q < kVec; ++q) acc[b][q] = T(0);
+    qwalk<1>(coords, uu, vv, table, nsteps, nmodes,
+             [&](int, int k, const T z[kVec]) {
+#pragma unroll
+                 for (int b = 0; b < NB; ++b) {
+                     const T c = coefs[int64_t(b) * nmodes + k];
+#pragma unroll
+                     for (int q = 0; q < kVec; ++q) acc[b][q] += c * z[q];
+                 }
+             },
+             [] {});
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        T* dst = out + int64_t(b) * npts;
+        if (accumulate) {
+            T old[kVec];
+            load_pts(dst, base, lane, npts, full, old);
+#pragma unroll
+            for (int q = 0; q < kVec; ++q) acc[b][q] += old[q];
+        }
+        store_pts<false>(dst, base, lane, npts, full, acc[b]);
+    }
+}
+
+// ---------------------------------------------------------------- projection: one partial per (workgroup, b, k)
+// As zernike_project_kernel: each wave sums its 64 x kVec points per step, reduces over its lanes and adds the total into an LDS slot
+// of its own, (wave, b, k); the workgroup adds its waves in order at the end and stores partial[group][b0 + b][k] (row length
+// ld = B * nmodes).  The butterflies of E = 8 / NB consecutive steps run together.
+template <typename T, int NB>
+__global__ __launch_bounds__(kThreads) void qpoly_project_kernel(int64_t npts, int coords, const T* __restrict__ u, const T* __restrict__ v,
+                                                                 const QStep<T>* __restrict__ table, int nsteps, int nmodes,
+                                                                 const T* __restrict__ g, T* __restrict__ partial, int64_t ld, int vec) {
+    constexpr int E = 8 / NB;
+    extern __shared__ __align__(16) unsigned char smem[];
+    T* sacc = reinterpret_cast<T*>(smem);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nacc = NB * nmodes;
+    for (int e = tid; e < kWaves * nacc; e += kThreads) sacc[e] = T(0);
+    __syncthreads();
+    T* wacc = sacc + wave * nacc;
+    // the wave stays together through the loop (a shuffle needs every lane) and masks its own tail
+    for (int64_t base = wave_tile(wave); base < npts; base += int64_t(gridDim.x) * kThreads * kVec) {
+        const bool full = vec && base + 64 * kVec <= npts;
+        T uu[kVec], vv[kVec], gg[NB][kVec], red[NB][E];
+        int slot[E];
+        load_coords(coords, u, v, base, lane, npts, full, uu, vv);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) load_pts(g + int64_t(b) * npts, base, lane, npts, full, gg[b]);
+#pragma unroll
+        for (int j = 0; j < E; ++j) slot[j] = -1;
+        qwalk<E>(coords, uu, vv, table, nsteps, nmodes,
+                 [&](int j, int k, const T z[kVec]) {
+                     slot[j] = k;
+#pragma unroll
+                     for (int b = 0; b < NB; ++b) {
+                         T s = T(0);
+#pragma unroll
+                         for (int q = 0; q < kVec; ++q) s += gg[b][q] * z[q];
+                         red[b][j] = s;
+                     }
+                 },
+                 [&] {
+#pragma unroll
+                     for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+                         for (int j = 0; j < E; ++j)
+#pragma unroll
+                             for (int b = 0; b < NB; ++b) red[b][j] += __shfl_xor(red[b][j], off);
+#pragma unroll
+                     for (int j = 0; j < E; ++j) {
+                         if (slot[j] >= 0 && lane == 0)
+#pragma unroll
+                             for (int b = 0; b < NB; ++b) wacc[b * nmodes + slot[j]] += red[b][j];
+                         slot[j] = -1;
+                     }
+                 });
+    }
+    __syncthreads();
+    for (int o = tid; o < nacc; o += kThreads) {
+        T s = sacc[o];
+        for (int w = 1; w < kWaves; ++w) s += sacc[w * nacc + o];
+        partial[int64_t(blockIdx.x) * ld + o] = s;
+    }
+}
+
+size_t elem_of(int32_t dtype) { return dtype == PM_F32 ? 4 : 8; }
+
+// 16-byte vectors: every plane of npts points starts on a 16-byte boundary, and so does every pointer given (null: not read)
+int vec_ok(int64_t npts, std::initializer_list<const void*> ptrs) {
+    if (npts % kVec) return 0;
+    for (const void* p : ptrs)
+        if (reinterpret_cast<uintptr_t>(p) % 16) return 0;
+    return 1;
+}
+
+int64_t tiles_of(int64_t npts) { return (npts + int64_t(kThreads) * kVec - 1) / (int64_t(kThreads) * kVec); }
+
+int64_t project_groups(int64_t npts) { return std::max<int64_t>(1, std::min<int64_t>(tiles_of(npts), kMaxProjectGroups)); }
+
+// the largest of 8, 4, 2, 1 coefficient vectors per projection walk whose per-wave accumulators fit kProjectLds
+int project_nb(int32_t dtype, int64_t nmodes, int64_t batch) {
+    for (int nb = 8; nb > 1; nb >>= 1)
+        if (nb <= batch && size_t(kWaves) * nb * size_t(nmodes) * elem_of(dtype) <= kProjectLds) return nb;
+    return 1;
+}
+
+int check_walk(const char* who, int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
+               int64_t nmodes) {
+    if (dtype != PM_F32 && dtype != PM_F64) return fail(PM_ERR_ARG, "%s: dtype must be PM_F32 or PM_F64", who);
+    if (coords != PM_ZERNIKE_CARTESIAN && coords != PM_ZERNIKE_POLAR && coords != PM_QPOLY_RADIAL)
+        return fail(PM_ERR_ARG, "%s: coords must be PM_ZERNIKE_CARTESIAN, PM_ZERNIKE_POLAR or PM_QPOLY_RADIAL", who);
+    if (!u || (!v && coords != PM_QPOLY_RADIAL) || !table || npts < 0 || nsteps < 0 || nmodes < 0 || nsteps > INT32_MAX ||
+        nmodes > INT32_MAX)
+        return fail(PM_ERR_ARG, "%s: bad argument (null pointer or negative size)", who);
+    if (tiles_of(npts) > INT32_MAX) return fail(PM_ERR_ARG, "%s: %lld points is too many", who, (long long)npts);
+    return 0;
+}
+
+template <typename T>
+void launch_basis(int64_t npts, int coords, const void* u, const void* v, const void* table, int nsteps, int nmodes, void* out, hipStream_t st) {
+    const dim3 grid{unsigned(tiles_of(npts))}, block{kThreads};
+    const int vec = vec_ok(npts, {u, v, out});
+    hipLaunchKernelGGL(qpoly_basis_kernel<T>, grid, block, 0, st, npts, coords, (const T*)u, (const T*)v, (const QStep<T>*)table, nsteps,
+                       nmodes, (T*)out, vec);
+}
+
+template <typename T>
+void launch_sum(int64_t npts, int coords, const void* u, const void* v, const void* table, int nsteps, int nmodes, int64_t batch,
+                const void* coefs, int accumulate, void* out, hipStream_t st) {
+    const dim3 grid{unsigned(tiles_of(npts))}, block{kThreads};
+    const int vec = vec_ok(npts, {u, v, out});
+    for (int64_t b0 = 0; b0 < batch;) {
+        const int64_t left = batch - b0;
+        const T* c = (const T*)coefs + b0 * nmodes;
+        T* o = (T*)out + b0 * npts;
+#define PM_QSUM(NB)                                                                                                                  \
+    hipLaunchKernelGGL((qpoly_sum_kernel<T, NB>), grid, block, 0, st, npts, coords, (const T*)u, (const T*)v, (const QStep<T>*)table, \
+                       nsteps, nmodes, c, accumulate, o, vec);                                                                          \
+    b0 += NB
+        if (left >= 8) { PM_QSUM(8); }
+        else if (left >= 4) { PM_QSUM(4); }
+        else if (left >= 2) { PM_QSUM(2); }
+        else { PM_QSUM(1); }
+#undef PM_QSUM
+    }
+}
+
+template <typename T>
+void launch_project(int64_t npts, int coords, const void* u, const void* v, const void* table, int nsteps, int nmodes, int64_t batch,
+                    const void* g, void* out, void* ws, int nb, hipStream_t st) {
+    const int64_t groups = project_groups(npts);
+    const dim3 grid{unsigned(groups)}, block{kThreads};
+    T* partial = (T*)ws;
+    const int vec = vec_ok(npts, {u, v, g});
+    for (int64_t b0 = 0; b0 < batch;) {
+        const int64_t left = batch - b0;
+        const T* gb = (const T*)g + b0 * npts;
+        T* pb = partial + b0 * nmodes;
+#define PM_QPROJ(NB)                                                                                                                \
+    hipLaunchKernelGGL((qpoly_project_kernel<T, NB>), grid, block, size_t(kWaves) * NB * nmodes * sizeof(T), st, npts, coords,       \
+                       (const T*)u, (const T*)v, (const QStep<T>*)table, nsteps, nmodes, gb, pb, batch * nmodes, vec);                      \
+    b0 += NB
+        if (nb >= 8 && left >= 8) { PM_QPROJ(8); }
+        else if (nb >= 4 && left >= 4) { PM_QPROJ(4); }
+        else if (nb >= 2 && left >= 2) { PM_QPROJ(2); }
+        else { PM_QPROJ(1); }
+#undef PM_QPROJ
+    }
+    hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(batch * nmodes)), block, 0, st, groups, batch * nmodes, (const T*)partial,
+                       (T*)out);
+}
+
+}  // namespace
+}  // namespace pm
+
+using namespace pm;
+
+extern "C" {
+
+int pm_qpoly_basis(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
+                   int64_t nmodes, void* out, void* stream) {
+    if (int rc = check_walk("pm_qpoly_basis", dtype, coords, npts, u, v, table, nsteps, nmodes)) return rc;
+    if (!out) return fail(PM_ERR_ARG, "pm_qpoly_basis: bad argument (null pointer)");
+    if (npts == 0 || nmodes == 0) return 0;
+    hipStream_t st = PM_STREAM(stream);
+    if (dtype == PM_F32)
+        launch_basis<float>(npts, coords, u, v, table, int(nsteps), int(nmodes), out, st);
+    else
+        launch_basis<double>(npts, coords, u, v, table, int(nsteps), int(nmodes), out, st);
+    return int(hipGetLastError());
+}
+
+int pm_qpoly_sum(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
+                 int64_t nmodes, int64_t batch, const void* coefs, int32_t accumulate, void* out, void* stream) {
+    if (int rc = check_walk("pm_qpoly_sum", dtype, coords, npts, u, v, table, nsteps, nmodes)) return rc;
+    if (!out || !coefs || batch < 0) return fail(PM_ERR_ARG, "pm_qpoly_sum: bad argument (null pointer or negative batch)");
+    if (npts == 0 || batch == 0) return 0;
+    hipStream_t st = PM_STREAM(stream);
+    if (dtype == PM_F32)
+        launch_sum<float>(npts, coords, u, v, table, int(nsteps), int(nmodes), batch, coefs, accumulate != 0, out, st);
+    else
+        launch_sum<double>(npts, coords, u, v, table, int(nsteps), int(nmodes), batch, coefs, accumulate != 0, out, st);
+    return int(hipGetLastError());
+}
+
+size_t pm_qpoly_project_workspace(int32_t dtype, int64_t npts, int64_t nmodes, int64_t batch) {
+    if ((dtype != PM_F32 && dtype != PM_F64) || npts < 0 || nmodes < 0 || batch < 0) return 0;
+    return size_t(project_groups(npts)) * size_t(batch) * size_t(nmodes) * elem_of(dtype);
+}
+
+int pm_qpoly_project(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
+                     int64_t nmodes, int64_t batch, const void* databar, void* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_walk("pm_qpoly_project", dtype, coords, npts, u, v, table, nsteps, nmodes)) return rc;
+    if (!out || !databar || batch < 0) return fail(PM_ERR_ARG, "pm_qpoly_project: bad argument (null pointer or negative batch)");
+    if (batch * nmodes > INT32_MAX) return fail(PM_ERR_ARG, "pm_qpoly_project: batch * nmodes is too large");
+    if (size_t(kWaves) * size_t(nmodes) * elem_of(dtype) > kProjectLds)
+        return fail(PM_ERR_UNSUPPORTED, "pm_qpoly_project: %lld modes do not fit the workgroup's accumulators", (long long)nmodes);
+    if (batch == 0 || nmodes == 0) return 0;
+    const size_t need = pm_qpoly_project_workspace(dtype, npts, nmodes, batch);
+    if (!workspace || workspace_bytes < need)
+        return fail(PM_ERR_WORKSPACE, "pm_qpoly_project: workspace of %zu bytes is smaller than the %zu pm_qpoly_project_workspace asks for",
+                    workspace_bytes, need);
+    hipStream_t st = PM_STREAM(stream);
+    const int nb = project_nb(dtype, nmodes, batch);
+    if (dtype == PM_F32)
+        launch_project<float>(npts, coords, u, v, table, int(nsteps), int(nmodes), batch, databar, out, workspace, nb, st);
+    else
+        launch_project<double>(npts, coords, u, v, table, int(nsteps), int(nmodes), batch, databar, out, workspace, nb, st);
+    return int(hipGetLastError());
+}
+
+}  // extern "C"
