@@ -405,6 +405,47 @@ size_t pm_qpoly_project_workspace(int32_t dtype, int64_t npts, int64_t nmodes, i
 int pm_qpoly_project(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
                      int64_t nmodes, int64_t batch, const void* databar, void* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Coordinates (csrc/geometry.hip): REAL arrays of dtype PM_F32 / PM_F64, computed in that precision. */
+
+/* make_xy_grid (prysm/coordinates.py:344-378) with fftrange (fttools.py:13-15): element j of an axis of n samples is (j - n / 2)
+ * converted to dtype, times dx rounded once to dtype.  grid != 0: x and y are ny x nx meshgrids; grid == 0: x holds nx and y ny values.
+ * Both outputs from one launch. */
+int pm_xy_grid(int32_t dtype, int64_t ny, int64_t nx, double dx, int32_t grid, void* x, void* y, void* stream);
+
+/* cart_to_polar (coordinates.py:73-102): rho = hypot(x, y), phi = atan2(y, x), ny x nx values each, one launch.  separable != 0: x
+ * holds nx and y ny values (the reference's vec_to_grid); else x and y hold ny x nx values. */
+int pm_cart_to_polar(int32_t dtype, int64_t ny, int64_t nx, int32_t separable, const void* x, const void* y, void* rho, void* phi,
+                     void* stream);
+
+/* polar_to_cart (coordinates.py:105-125): x = rho cos(phi), y = rho sin(phi) for n points, one launch. */
+int pm_polar_to_cart(int32_t dtype, int64_t n, const void* rho, const void* phi, void* x, void* y, void* stream);
+
+/* Aperture geometry (csrc/geometry.hip): a tree of the signed-distance shapes of prysm/geometry.py, combined on the distance and
+ * turned into an array once, in ONE launch that writes every output element once.  Replaces the array sweeps of antialias
+ * (geometry.py:11-34), union / intersect / subtract (37-93), gaussian (154-179), rectangle_sdf (182-222), rotated_ellipse_sdf
+ * (251-290), circle_sdf (337-353), annulus_sdf (375-395), polygon_sdf (419-463), regular_polygon_sdf (466-491), spider_sdf (550-594),
+ * offset_circle (627-653), rectangle_with_corner_fillets_sdf (656-696) and of the `<= 0` of their mask forms.
+ *
+ * `table` is a DEVICE array of batch x nsteps steps built by prysm_amd/geometry_plan.py (struct pm::GStep: int32 op, comb, slot, flags;
+ * T f[8] -- 48 bytes for PM_F32, 80 for PM_F64), program b at table + b * nsteps.  A step evaluates (a part of) a primitive at the
+ * point: op 1 circle / 2 annulus about (f0, f1) with radius f2 (half-width f3); 3 / 4 the same on a RADIAL coordinate taken from x;
+ * 5 rectangle (coordinates rotated by (cos, sin) = (f0, f1) when flag ROT, then centre (f2, f3), half-sizes f4, f5, fillet f6);
+ * 6 ellipse (cos f0, sin f1, axes f2, f3 and their squares f4, f5); 7 one polygon edge from (f0, f1) along (f2, f3), f4 = 1 / |e|^2,
+ * f5 the end's y, flag UP = it rises; 8 one spider vane (cos f0, sin f1, root (f2, f3), half-width f4); 9 gaussian; 10 MERGE (the
+ * value is accumulator slot + 1); 0 nothing.  Flag BEGIN starts a primitive of several steps (edges, vanes: running min / crossing
+ * parity), flag END finishes it and combines it into accumulator `slot` (0 .. 3) by comb: 0 set, 1 min, 2 max, 3 max(acc, -value).
+ * The result is accumulator 0.
+ *
+ * coords: PM_COORDS_GRID computes x = T(j - ox) * T(dx), y = T(i - oy) * T(dy) from the pixel index (x, y not read, may be NULL);
+ * PM_COORDS_SEPARABLE reads x (nx values) and y (ny values); PM_COORDS_POINTWISE reads x and y of ny x nx values each (contiguous).
+ * out_kind: PM_SDF_MASK writes 1-byte booleans d <= 0, PM_SDF_DISTANCE d, PM_SDF_COVERAGE min(max(0.5 - d / aa_dx, 0), 1) in dtype.
+ * out: batch x ny x nx elements with out_ld elements between rows and out_bstride between programs. */
+enum { PM_COORDS_GRID = 0, PM_COORDS_SEPARABLE = 1, PM_COORDS_POINTWISE = 2 };
+enum { PM_SDF_MASK = 0, PM_SDF_DISTANCE = 1, PM_SDF_COVERAGE = 2 };
+int pm_sdf_render(int32_t dtype, int32_t coords, int64_t ny, int64_t nx, const void* x, const void* y, int64_t ox, int64_t oy, double dx,
+                  double dy, const void* table, int64_t nsteps, int64_t batch, int32_t out_kind, double aa_dx, void* out, int64_t out_ld,
+                  int64_t out_bstride, void* stream);
+
 /* Segmented apertures (csrc/segmented.hip): CompositeHexagonalAperture.compose_opd (prysm/segmented.py:178-285) and its adjoint.
  * The grid is rows x cols REAL points (dtype PM_F32 / PM_F64, computed in that precision); x, y are the aperture's DEVICE coordinate
  * arrays.  `plan` is a DEVICE array of nseg 80-byte segment records built by prysm_amd/segmented.py (struct pm::SegDesc: int32 y0, x0,

@@ -26,6 +26,8 @@ PM_LATTICE_SCATTER, PM_LATTICE_GATHER = 0, 1
 PM_ZERNIKE_CARTESIAN, PM_ZERNIKE_POLAR = 0, 1
 PM_QPOLY_RADIAL = 2
 PM_SEGMENT_ZERNIKE, PM_SEGMENT_STORED = 0, 1
+PM_COORDS_GRID, PM_COORDS_SEPARABLE, PM_COORDS_POINTWISE = 0, 1, 2
+PM_SDF_MASK, PM_SDF_DISTANCE, PM_SDF_COVERAGE = 0, 1, 2
 
 c_i32, c_i64, c_f64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
 
@@ -106,6 +108,11 @@ SIGNATURES = {
     'pm_qpoly_sum': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp]),
     'pm_qpoly_project_workspace': (c_sz, [c_i32, c_i64, c_i64, c_i64]),
     'pm_qpoly_project': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'pm_xy_grid': (c_i32, [c_i32, c_i64, c_i64, c_f64, c_i32, c_vp, c_vp, c_vp]),
+    'pm_cart_to_polar': (c_i32, [c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'pm_polar_to_cart': (c_i32, [c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'pm_sdf_render': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_f64, c_f64, c_vp, c_i64, c_i64, c_i32, c_f64, c_vp,
+                              c_i64, c_i64, c_vp]),
     'pm_segment_plan_check': (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64]),
     'pm_segment_compose': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                    c_vp, c_i32, c_vp, c_vp]),

@@ -1,0 +1,101 @@
+"""Coordinate grids and conversions on the device (prysm/coordinates.py:11-125, 344-378).
+
+make_xy_grid, cart_to_polar and polar_to_cart are one launch each, both outputs from one kernel (csrc/geometry.hip); the two view
+helpers are host logic on tensors.  Grids come back in config.precision, conversions in the inputs' precision (float32 when every
+input is float32, float64 otherwise).  The rest of the reference module (homographies, warps, resampling, quadratures) is not here.
+"""
+import numpy as np
+import torch
+
+from . import _lib as L
+from .conf import config
+from .geometry_plan import grid_spacing
+
+__all__ = ['make_xy_grid', 'cart_to_polar', 'polar_to_cart', 'optimize_xy_separable', 'broadcast_1d_to_2d']
+
+
+def _real_dtype(*arrays, what='coordinates'):
+    """float32 when every array is float32, float64 for any other real input; TypeError for complex"""
+    f32 = True
+    for a in arrays:
+        if isinstance(a, torch.Tensor):
+            cplx, single = a.is_complex(), a.dtype == torch.float32
+        else:
+            dt = np.asarray(a).dtype
+            cplx, single = np.issubdtype(dt, np.complexfloating), dt == np.float32
+        if cplx:
+            raise TypeError(f'{what} must be real')
+        f32 = f32 and single
+    return torch.float32 if f32 else torch.float64
+
+
+def _code(dt):
+    return L.PM_F32 if dt == torch.float32 else L.PM_F64
+
+
+def _tensor(a):
+    return a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
+
+
+def optimize_xy_separable(x, y):
+    """x as a (1, nx) row and y as an (ny, 1) column: views of the first row / first column of 2-D meshgrids, or of 1-D vectors
+    (coordinates.py:11-45)."""
+    x, y = _tensor(x), _tensor(y)
+    if x.ndim == 2:
+        return x[0, :].reshape(1, -1), y[:, 0].reshape(-1, 1)
+    return x.reshape(1, -1), y.reshape(-1, 1)
+
+
+def broadcast_1d_to_2d(x, y):
+    """vectors x (n,) and y (m,) as (m, n) views (coordinates.py:48-70)."""
+    x, y = _tensor(x), _tensor(y)
+    return x.reshape(1, -1).expand(y.numel(), x.numel()), y.reshape(-1, 1).expand(y.numel(), x.numel())
+
+
+def make_xy_grid(shape, *, dx=0, diameter=0, grid=True):
+    """x, y of a grid of `shape` = (rows, cols) samples (a scalar: square) spaced dx apart, or diameter / max(shape) when a diameter is
+    given, with the origin at sample n // 2: meshgrids, or 1-D vectors when grid=False (coordinates.py:344-378).  Element j of an axis
+    is (j - n // 2) in config.precision times dx rounded once to it, the reference's fftrange(n) * dx bit for bit.  One launch."""
+    (ny, nx), dx = grid_spacing(shape, dx, diameter)
+    dt = L.torch_dtype(config.compute_precision)
+    dev = L.device()
+    if grid:
+        x, y = torch.empty((ny, nx), dtype=dt, device=dev), torch.empty((ny, nx), dtype=dt, device=dev)
+    else:
+        x, y = torch.empty(nx, dtype=dt, device=dev), torch.empty(ny, dtype=dt, device=dev)
+    L.check(L.load().pm_xy_grid(_code(dt), ny, nx, dx, int(bool(grid)), L.ptr(x), L.ptr(y), L.stream_ptr()))
+    return x, y
+
+
+def cart_to_polar(x, y, vec_to_grid=True):
+    """rho = hypot(x, y), phi = atan2(y, x) (coordinates.py:73-102).  1-D vectors give (ny, nx) grids when vec_to_grid; otherwise the
+    inputs broadcast.  One launch."""
+    dt = _real_dtype(x, y)
+    sx, sy = tuple(np.shape(x)), tuple(np.shape(y))
+    separable = vec_to_grid and len(sx) == 1
+    if separable:
+        if len(sy) != 1:
+            raise ValueError(f'x is a vector of {sx} but y has shape {sy}')
+        shape = (sy[0], sx[0])
+    else:
+        shape = tuple(np.broadcast_shapes(sx, sy))
+    xd, yd = L.as_device(x, dt), L.as_device(y, dt)
+    if not separable and (sx != shape or sy != shape):
+        xd, yd = xd.expand(shape).contiguous(), yd.expand(shape).contiguous()
+    rho, phi = torch.empty(shape, dtype=dt, device=xd.device), torch.empty(shape, dtype=dt, device=xd.device)
+    n = rho.numel()
+    ny, nx = (shape if separable else (1, n))
+    L.check(L.load().pm_cart_to_polar(_code(dt), ny, nx, int(separable), L.ptr(xd), L.ptr(yd), L.ptr(rho), L.ptr(phi), L.stream_ptr()))
+    return rho, phi
+
+
+def polar_to_cart(rho, phi):
+    """x = rho cos(phi), y = rho sin(phi) (coordinates.py:105-125).  One launch."""
+    dt = _real_dtype(rho, phi)
+    shape = tuple(np.broadcast_shapes(tuple(np.shape(rho)), tuple(np.shape(phi))))
+    r, p = L.as_device(rho, dt), L.as_device(phi, dt)
+    if tuple(r.shape) != shape or tuple(p.shape) != shape:
+        r, p = r.expand(shape).contiguous(), p.expand(shape).contiguous()
+    x, y = torch.empty(shape, dtype=dt, device=r.device), torch.empty(shape, dtype=dt, device=r.device)
+    L.check(L.load().pm_polar_to_cart(_code(dt), x.numel(), L.ptr(r), L.ptr(p), L.ptr(x), L.ptr(y), L.stream_ptr()))
+    return x, y
