@@ -446,6 +446,44 @@ int pm_sdf_render(int32_t dtype, int32_t coords, int64_t ny, int64_t nx, const v
                   double dy, const void* table, int64_t nsteps, int64_t batch, int32_t out_kind, double aa_dx, void* out, int64_t out_ld,
                   int64_t out_bstride, void* stream);
 
+/* The detector (csrc/detector.hip): prysm/detector.py's bindown (222-274), tile (277-339) and Detector.expose (83-148).
+ *
+ * pm_bindown: out (batch x my x nx) = the bins of fy x fx elements of in (batch x my fy x nx fx), summed (PM_BIN_SUM) or averaged
+ * (PM_BIN_AVG: the sum divided by fy fx).  Each bin is one running sum in dtype, its rows in order and left to right within a row, so
+ * the result is bitwise reproducible.  pm_tile is the adjoint: out (batch x my fy x nx fx) = every element of in (batch x my x nx)
+ * repeated fy x fx times, times `scale`.  Leading dimensions and batch strides in elements; one launch each, no atomics. */
+enum { PM_BIN_AVG = 0, PM_BIN_SUM = 1 };
+int pm_bindown(int32_t dtype, int64_t batch, int64_t my, int64_t nx, int64_t fy, int64_t fx, int32_t mode, const void* in, int64_t in_ld,
+               int64_t in_bstride, void* out, int64_t out_ld, int64_t out_bstride, void* stream);
+int pm_tile(int32_t dtype, int64_t batch, int64_t my, int64_t nx, int64_t fy, int64_t fx, double scale, const void* in, int64_t in_ld,
+            int64_t in_bstride, void* out, int64_t out_ld, int64_t out_bstride, void* stream);
+
+/* The deterministic tail of an exposure, in fp64 whatever dtype the electrons have: + bias, clip at fwc, times 1 / conversion_gain,
+ * clip to [0, 2^bits - 1], truncation toward zero, then lut[DN] when lut is not NULL (a DEVICE table of lut_len >= 2^bits elements
+ * of out_bytes bytes each).  electrons: batch x ny x nx (PM_F32 / PM_F64) with ld elements between rows and bstride between
+ * members; out: contiguous, elements of out_bytes (1, 2, 4 or 8) bytes; without a LUT 8 * out_bytes >= bits. */
+int pm_detector_digitize(int32_t dtype, int64_t batch, int64_t ny, int64_t nx, const void* electrons, int64_t ld, int64_t bstride, double bias,
+                         double fwc, double conversion_gain, int32_t bits, const void* lut, int64_t lut_len, int32_t out_bytes, void* out,
+                         void* stream);
+
+/* Detector.expose fused: `frames` noisy exposures of img (batch x ny x nx, strided like pm_detector_digitize's input) into out
+ * (frames x batch x ny x nx, contiguous, out_bytes per element), one launch plus a one-thread launch that advances the state.
+ * Per pixel: mean = img * exposure_time * prnu + dark_current * exposure_time * dcnu in fp64 (prnu, dcnu: DEVICE fp64 maps of ny x nx,
+ * contiguous, shared by the members; NULL = 1); per frame: shot ~ Poisson(mean) (exact: inversion below a mean of 10, Hoermann's PTRS
+ * from there), read = read_noise * N(0, 1) (nothing drawn when read_noise == 0), then the tail of pm_detector_digitize.  Random
+ * words are Philox4x32-10 with key = seed and counter = (pixel low word, pixel high word, (state[0] + frame) mod 2^32, draw block);
+ * pixel = pixel_offset + the row-major index into the stack.  `state` is a DEVICE array of two int64: [0] the exposure index (frames
+ * exposed so far), read by the kernel and advanced by `frames` after it on the same stream; [1] a status word that is set to 1 when
+ * a mean is negative, NaN or infinite (such a pixel gets 0 shot electrons).  prysm_amd/detector_plan.py is the same arithmetic in numpy. */
+int pm_detector_expose(int32_t dtype, int64_t batch, int64_t ny, int64_t nx, const void* img, int64_t ld, int64_t bstride, const void* prnu,
+                       const void* dcnu, double exposure_time, double dark_current, double read_noise, double bias, double fwc,
+                       double conversion_gain, int32_t bits, const void* lut, int64_t lut_len, int32_t out_bytes, int64_t frames, int64_t seed,
+                       int64_t pixel_offset, void* state, void* out, void* stream);
+
+/* The four Philox words of draw block `block` of the pixels pixel0 .. pixel0 + npix - 1 at global frame index `frame`, to out (npix x 4
+ * uint32): what the tests pin the kernels' generator with. */
+int pm_detector_words(int64_t seed, int64_t pixel0, int64_t npix, int64_t frame, int32_t block, void* out, void* stream);
+
 /* Segmented apertures (csrc/segmented.hip): CompositeHexagonalAperture.compose_opd (prysm/segmented.py:178-285) and its adjoint.
  * The grid is rows x cols REAL points (dtype PM_F32 / PM_F64, computed in that precision); x, y are the aperture's DEVICE coordinate
  * arrays.  `plan` is a DEVICE array of nseg 80-byte segment records built by prysm_amd/segmented.py (struct pm::SegDesc: int32 y0, x0,

@@ -28,6 +28,7 @@ PM_QPOLY_RADIAL = 2
 PM_SEGMENT_ZERNIKE, PM_SEGMENT_STORED = 0, 1
 PM_COORDS_GRID, PM_COORDS_SEPARABLE, PM_COORDS_POINTWISE = 0, 1, 2
 PM_SDF_MASK, PM_SDF_DISTANCE, PM_SDF_COVERAGE = 0, 1, 2
+PM_BIN_AVG, PM_BIN_SUM = 0, 1
 
 c_i32, c_i64, c_f64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
 
@@ -113,6 +114,13 @@ SIGNATURES = {
     'pm_polar_to_cart': (c_i32, [c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'pm_sdf_render': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_f64, c_f64, c_vp, c_i64, c_i64, c_i32, c_f64, c_vp,
                               c_i64, c_i64, c_vp]),
+    'pm_bindown': (c_i32, [c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp]),
+    'pm_tile': (c_i32, [c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_f64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp]),
+    'pm_detector_digitize': (c_i32, [c_i32, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_f64, c_f64, c_f64, c_i32, c_vp, c_i64, c_i32, c_vp,
+                                     c_vp]),
+    'pm_detector_expose': (c_i32, [c_i32, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_i32,
+                                   c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    'pm_detector_words': (c_i32, [c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp]),
     'pm_segment_plan_check': (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64]),
     'pm_segment_compose': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                    c_vp, c_i32, c_vp, c_vp]),
@@ -187,6 +195,8 @@ _NP2TORCH = {
     np.dtype('float32'): torch.float32, np.dtype('float64'): torch.float64, np.dtype('float16'): torch.float16,
     np.dtype('complex64'): torch.complex64, np.dtype('complex128'): torch.complex128, np.dtype('bool'): torch.bool,
     np.dtype('int32'): torch.int32, np.dtype('int64'): torch.int64, np.dtype('uint8'): torch.uint8,
+    np.dtype('uint16'): torch.uint16, np.dtype('uint32'): torch.uint32, np.dtype('uint64'): torch.uint64, np.dtype('int16'): torch.int16,
+    np.dtype('int8'): torch.int8,
 }
 
 
