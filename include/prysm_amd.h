@@ -242,6 +242,11 @@ int pm_fft1_ramp(int32_t dtype, int32_t direction, int32_t axis, int64_t nseq, i
                  int64_t in_ld, void* out, int64_t out_ld, void* stream);
 
 /* --- pointwise / synthesis kernels -------------------------------------------------------- */
+/* Every 2-D array of these entry points is row-major with a leading dimension in ELEMENTS (`*_ld`): element [r][c] lies at
+ * base + r * ld + c, any ld >= cols and any element-aligned base.  A leading dimension below the number of columns is refused with
+ * PM_ERR_ARG before anything is launched -- by pm_spline_prefilter, pm_encircled_energy and pm_encircled_energy_adjoint always, by
+ * the others when the array has more than one row (for one row they take any value).  Nothing outside the rows x cols window of an
+ * output is written (tests/test_gpu_pointwise.py). */
 
 /* out = a * b (op 0), a * conj(b) (op 1); complex, same shape (rows x cols).
  * Wavefront.__mul__ (prysm/propagation/wavefront.py:360-411), _adjoint_multiply (_kernels.py:29-37). */

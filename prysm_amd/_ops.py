@@ -417,10 +417,19 @@ def fft1_ramp(x, K, axis, direction, *, pre=None, post=None, out_len, conj=False
     return out
 
 
+def _rows2d(t):
+    """`t` as the kernels address a 2-D array: unit column stride, rows at least a row apart.  A column-strided, transposed or
+    row-broadcast view is copied (the entry points take one leading dimension per array and nothing else)."""
+    if t.stride(-1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t
+
+
 def cmul(a, b, conj_b=False):
     lib = L.load()
-    out = torch.empty_like(a)
+    a, b = _rows2d(a), _rows2d(b)
     rows, cols = a.shape
+    out = torch.empty((rows, cols), dtype=a.dtype, device=a.device)
     L.check(lib.pm_cmul(L.code(a), 1 if conj_b else 0, rows, cols, L.ptr(a), a.stride(0), L.ptr(b), b.stride(0),
                         L.ptr(out), out.stride(0), L.stream_ptr()))
     return out
@@ -429,8 +438,9 @@ def cmul(a, b, conj_b=False):
 def rmul(r, a, scale=1.0):
     """scale * r * a for a REAL image r and a complex field a of the matching precision (pm_rmul; one sweep)."""
     lib = L.load()
-    out = torch.empty_like(a)
+    r, a = _rows2d(r), _rows2d(a)
     rows, cols = a.shape
+    out = torch.empty((rows, cols), dtype=a.dtype, device=a.device)
     L.check(lib.pm_rmul(L.code(a), rows, cols, L.ptr(r), r.stride(0), L.ptr(a), a.stride(0), float(scale), L.ptr(out), out.stride(0),
                         L.stream_ptr()))
     return out
@@ -439,8 +449,9 @@ def rmul(r, a, scale=1.0):
 def scale_sep(x, row_vec=None, col_vec=None, row_conj=False, col_conj=False, scale=1.0):
     """out[i, j] = x[i, j] * row_vec[i] * col_vec[j] * scale (row_vec indexes rows, col_vec columns)."""
     lib = L.load()
-    out = torch.empty_like(x)
+    x = _rows2d(x)
     rows, cols = x.shape
+    out = torch.empty((rows, cols), dtype=x.dtype, device=x.device)
     L.check(lib.pm_scale_sep(L.code(x), rows, cols, L.ptr(x), x.stride(0), L.ptr(row_vec), 1 if row_conj else 0,
                              L.ptr(col_vec), 1 if col_conj else 0, float(scale), L.ptr(out), out.stride(0),
                              L.stream_ptr()))
@@ -450,11 +461,14 @@ def scale_sep(x, row_vec=None, col_vec=None, row_conj=False, col_conj=False, sca
 def abs2(x, out=None, weight=None):
     """|x|^2, or out += weight * |x|^2 when `out` and `weight` are given."""
     lib = L.load()
+    x = _rows2d(x)
     rows, cols = x.shape
     acc = 0
     if out is None:
         out = torch.empty((rows, cols), dtype=L._REAL_OF[x.dtype], device=x.device)
     else:
+        if out.stride(-1) != 1 or (rows > 1 and out.stride(0) < cols):
+            raise ValueError('abs2: `out` must have unit column stride and rows that do not overlap')
         _bump(out)
         if weight is not None:
             acc = 1
@@ -466,6 +480,7 @@ def abs2(x, out=None, weight=None):
 def abs_arg(x):
     """(|x|, angle(x)) of a complex 2-D array in one sweep (pm_abs_arg)."""
     lib = L.load()
+    x = _rows2d(x)
     rows, cols = x.shape
     rd = L._REAL_OF[x.dtype]
     oabs = torch.empty((rows, cols), dtype=rd, device=x.device)

@@ -467,6 +467,14 @@ using namespace pm;
 
 #define PM_STREAM(s) reinterpret_cast<hipStream_t>(s)
 
+// rows of a rows x cols window lie `ld` elements apart: with more than one row a leading dimension below cols would make rows overlap
+// (and an output race); one row takes any value (the wrappers pass the length there)
+static inline bool ld_ok(int64_t rows, int64_t cols, int64_t ld) { return rows <= 1 || ld >= cols; }
+#define PM_CHECK_LD(name, cond)                                                                                        \
+    do {                                                                                                               \
+        if (!(cond)) return fail(PM_ERR_ARG, name ": a leading dimension is smaller than the number of columns");      \
+    } while (0)
+
 // ---------------------------------------------------------------- real-input 2-D spectrum from the transform of the packed array
 // A real M x N array (N even) read as M x N/2 complex numbers z[r][j] = x[r][2j] + i x[r][2j+1] costs nothing to form -- it is the same
 // memory -- and its 2-D transform Zf (any route of pm_fft2: engine, mixed-radix, Bluestein) is half the work of transforming x as
@@ -605,6 +613,7 @@ int pm_r2c_untangle(int32_t dtype, int64_t M, int64_t N, const void* zf, int64_t
 int pm_cmul(int32_t dtype, int32_t op, int64_t rows, int64_t cols, const void* a, int64_t a_ld, const void* b,
             int64_t b_ld, void* out, int64_t out_ld, void* stream) {
     if (!a || !b || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_cmul: bad argument");
+    PM_CHECK_LD("pm_cmul", ld_ok(rows, cols, a_ld) && ld_ok(rows, cols, b_ld) && ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
     if (dtype == PM_C64) return cmul_launch<float>(op, rows, cols, a, a_ld, b, b_ld, out, out_ld, PM_STREAM(stream));
     if (dtype == PM_C128) return cmul_launch<double>(op, rows, cols, a, a_ld, b, b_ld, out, out_ld, PM_STREAM(stream));
@@ -614,6 +623,7 @@ int pm_cmul(int32_t dtype, int32_t op, int64_t rows, int64_t cols, const void* a
 int pm_rmul(int32_t dtype, int64_t rows, int64_t cols, const void* r, int64_t r_ld, const void* a, int64_t a_ld, double scale,
             void* out, int64_t out_ld, void* stream) {
     if (!r || !a || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_rmul: bad argument");
+    PM_CHECK_LD("pm_rmul", ld_ok(rows, cols, r_ld) && ld_ok(rows, cols, a_ld) && ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
     dim3 block;
     dim3 grid = grid2d(rows, cols, block);
@@ -632,6 +642,7 @@ int pm_scale_sep(int32_t dtype, int64_t rows, int64_t cols, const void* in, int6
                  int32_t ry_conj, const void* cxv, int32_t cx_conj, double scale, void* out, int64_t out_ld,
                  void* stream) {
     if (!in || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_scale_sep: bad argument");
+    PM_CHECK_LD("pm_scale_sep", ld_ok(rows, cols, in_ld) && ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
     dim3 block;
     dim3 grid = grid2d(rows, cols, block);
@@ -649,6 +660,7 @@ int pm_scale_sep(int32_t dtype, int64_t rows, int64_t cols, const void* in, int6
 int pm_abs2(int32_t dtype, int64_t rows, int64_t cols, const void* in, int64_t in_ld, void* out, int64_t out_ld,
             int32_t accumulate, double weight, void* stream) {
     if (!in || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_abs2: bad argument");
+    PM_CHECK_LD("pm_abs2", ld_ok(rows, cols, in_ld) && ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
     dim3 block;
     dim3 grid = grid2d(rows, cols, block);
@@ -671,6 +683,7 @@ int pm_abs2(int32_t dtype, int64_t rows, int64_t cols, const void* in, int64_t i
 int pm_abs_arg(int32_t dtype, int64_t rows, int64_t cols, const void* in, int64_t in_ld, void* out_abs, int64_t abs_ld, void* out_arg,
                int64_t arg_ld, void* stream) {
     if (!in || (!out_abs && !out_arg) || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_abs_arg: bad argument");
+    PM_CHECK_LD("pm_abs_arg", ld_ok(rows, cols, in_ld) && (!out_abs || ld_ok(rows, cols, abs_ld)) && (!out_arg || ld_ok(rows, cols, arg_ld)));
     if (rows == 0 || cols == 0) return 0;
     dim3 block;
     dim3 grid = grid2d(rows, cols, block);
@@ -688,6 +701,7 @@ int pm_abs_arg(int32_t dtype, int64_t rows, int64_t cols, const void* in, int64_
 int pm_sum_modes(int32_t dtype, int64_t nmodes, int64_t rows, int64_t cols, const void* modes, int64_t mode_stride,
                  int64_t modes_ld, const double* weights, int32_t accumulate, void* out, int64_t out_ld, void* stream) {
     if (!modes || !out || (!weights && nmodes > 0) || rows < 0 || cols < 0 || nmodes < 0) return fail(PM_ERR_ARG, "pm_sum_modes: bad argument");
+    PM_CHECK_LD("pm_sum_modes", ld_ok(rows, cols, modes_ld) && ld_ok(rows, cols, out_ld));
     if (dtype != PM_C64 && dtype != PM_C128) return fail(PM_ERR_ARG, "pm_sum_modes: dtype must be PM_C64 (float images) or PM_C128 (double)");
     if (rows == 0 || cols == 0) return 0;
     dim3 block;
@@ -721,6 +735,7 @@ int pm_sample_map(int32_t dtype, int32_t order, int64_t map_rows, int64_t map_co
                   void* out, int64_t out_ld, void* stream) {
     if (!map || !xf || !yf || !out || rows < 0 || cols < 0 || map_rows < 1 || map_cols < 1 || !(dx != 0.0))
         return fail(PM_ERR_ARG, "pm_sample_map: bad argument");
+    PM_CHECK_LD("pm_sample_map", ld_ok(map_rows, map_cols, map_ld) && (!fill || ld_ok(rows, cols, fill_ld)) && ld_ok(rows, cols, out_ld));
     if (order != 0 && order != 1) return fail(PM_ERR_UNSUPPORTED, "pm_sample_map: spline order must be 0 or 1");
     if (rows == 0 || cols == 0) return 0;
     dim3 block;
@@ -769,6 +784,7 @@ int pm_sample_spline(int32_t dtype, int32_t order, int64_t map_rows, int64_t map
     if (!coeff || !xf || !yf || !out || rows < 0 || cols < 0 || map_rows < 1 || map_cols < 1 || !(dx != 0.0) ||
         coeff_ld < map_cols + 2 * kSplinePad)
         return fail(PM_ERR_ARG, "pm_sample_spline: bad argument");
+    PM_CHECK_LD("pm_sample_spline", (!fill || ld_ok(rows, cols, fill_ld)) && ld_ok(rows, cols, out_ld));
     if (order < 2 || order > 5) return fail(PM_ERR_UNSUPPORTED, "pm_sample_spline: spline order must be 2 .. 5 (pm_sample_map serves 0 and 1)");
     if (rows == 0 || cols == 0) return 0;
     dim3 block;
@@ -790,6 +806,7 @@ int pm_sample_spline(int32_t dtype, int32_t order, int64_t map_rows, int64_t map
 int pm_pupil_synth(int32_t dtype, int64_t rows, int64_t cols, const void* amp, int32_t amp_dtype, int64_t amp_ld,
                    const void* opd, int64_t opd_ld, double k, void* out, int64_t out_ld, void* stream) {
     if (!opd || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_pupil_synth: bad argument");
+    PM_CHECK_LD("pm_pupil_synth", (!amp || ld_ok(rows, cols, amp_ld)) && ld_ok(rows, cols, opd_ld) && ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
     dim3 block;
     dim3 grid = grid2d(rows, cols, block);
@@ -816,6 +833,7 @@ int pm_pupil_synth(int32_t dtype, int64_t rows, int64_t cols, const void* amp, i
 int pm_quadratic_phase(int32_t dtype, int64_t rows, int64_t cols, const void* x, int64_t x_ld, const void* y,
                        int64_t y_ld, double c, void* out, int64_t out_ld, void* stream) {
     if (!x || !y || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_quadratic_phase: bad argument");
+    PM_CHECK_LD("pm_quadratic_phase", ld_ok(rows, cols, x_ld) && ld_ok(rows, cols, y_ld) && ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
     dim3 block;
     dim3 grid = grid2d(rows, cols, block);
@@ -848,6 +866,7 @@ int pm_as_tf_vectors(int32_t dtype, int64_t rows, int64_t cols, double wvl_um, d
 int pm_outer(int32_t dtype, int64_t rows, int64_t cols, const void* hy, const void* hx, void* out, int64_t out_ld,
              void* stream) {
     if (!hy || !hx || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_outer: bad argument");
+    PM_CHECK_LD("pm_outer", ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
     dim3 block;
     dim3 grid = grid2d(rows, cols, block);
@@ -863,6 +882,7 @@ int pm_outer(int32_t dtype, int64_t rows, int64_t cols, const void* hy, const vo
 int pm_embed(int32_t elem_bytes, int64_t irows, int64_t icols, const void* in, int64_t in_ld, int64_t orows,
              int64_t ocols, int64_t off_y, int64_t off_x, const void* fill, void* out, int64_t out_ld, void* stream) {
     if (!in || !out || irows < 0 || icols < 0 || orows < 0 || ocols < 0) return fail(PM_ERR_ARG, "pm_embed: bad argument");
+    PM_CHECK_LD("pm_embed", ld_ok(irows, icols, in_ld) && ld_ok(orows, ocols, out_ld));
     if (orows == 0 || ocols == 0) return 0;
     dim3 block;
     dim3 grid = grid2d(orows, ocols, block);
@@ -889,6 +909,7 @@ int pm_pad_index(int32_t elem_bytes, int32_t mode, int64_t irows, int64_t icols,
                  int64_t ocols, int64_t off_y, int64_t off_x, void* out, int64_t out_ld, void* stream) {
     if (!in || !out || irows < 1 || icols < 1 || orows < 0 || ocols < 0 || mode < 1 || mode > 4)
         return fail(PM_ERR_ARG, "pm_pad_index: bad argument");
+    PM_CHECK_LD("pm_pad_index", ld_ok(irows, icols, in_ld) && ld_ok(orows, ocols, out_ld));
     if (orows == 0 || ocols == 0) return 0;
     dim3 block;
     dim3 grid = grid2d(orows, ocols, block);
@@ -909,6 +930,7 @@ int pm_pad_index(int32_t elem_bytes, int32_t mode, int64_t irows, int64_t icols,
 int pm_mdft_basis(int32_t dtype, int64_t M, int64_t N, const void* f, const void* x, int32_t sign, void* E,
                   int64_t E_ld, void* stream) {
     if (!f || !x || !E || M < 0 || N < 0 || (sign != 1 && sign != -1)) return fail(PM_ERR_ARG, "pm_mdft_basis: bad argument");
+    PM_CHECK_LD("pm_mdft_basis", ld_ok(M, N, E_ld));
     if (M == 0 || N == 0) return 0;
     dim3 block;
     dim3 grid = grid2d(M, N, block);
@@ -924,6 +946,7 @@ int pm_mdft_basis(int32_t dtype, int64_t M, int64_t N, const void* f, const void
 int pm_mdft_basis_grid(int32_t dtype, int64_t M, int64_t N, double f_step, double f_shift, double f_scale, double x_step,
                        int32_t sign, void* E, int64_t E_ld, void* stream) {
     if (!E || M < 0 || N < 0 || (sign != 1 && sign != -1)) return fail(PM_ERR_ARG, "pm_mdft_basis_grid: bad argument");
+    PM_CHECK_LD("pm_mdft_basis_grid", ld_ok(M, N, E_ld));
     if (M == 0 || N == 0) return 0;
     dim3 block;
     dim3 grid = grid2d(M, N, block);
