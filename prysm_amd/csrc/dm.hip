@@ -13,7 +13,7 @@
 // inside, taps past an edge read the coefficients mirrored about it.  Coordinates are computed in fp64 in both precisions.
 #include "pm_internal.h"
 
-#define PM_STREAM(s) reinterpret_cast<hipStream_t>(s)
+#include "pm_entry.h"
 
 namespace pm {
 namespace {

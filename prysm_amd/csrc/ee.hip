@@ -6,7 +6,7 @@
 // results are reproducible run to run.
 #include "pm_internal.h"
 
-#define PM_STREAM(s) reinterpret_cast<hipStream_t>(s)
+#include "pm_entry.h"
 
 namespace pm {
 

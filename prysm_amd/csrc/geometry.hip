@@ -22,7 +22,7 @@
 
 #include "pm_internal.h"
 
-#define PM_STREAM(s) reinterpret_cast<hipStream_t>(s)
+#include "pm_entry.h"
 
 namespace pm {
 namespace {

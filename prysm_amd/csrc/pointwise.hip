@@ -1,20 +1,35 @@
 // Bandwidth-bound pointwise / synthesis kernels of the propagation path (gfx950).
 //
-// All of them are 2-D row-major with a leading dimension; one thread handles VEC adjacent
-// elements of a row (16 B per lane where the shape allows), grid-stride over rows so the launch
-// has >> 256 workgroups without exceeding ~2048.  Phases are reduced in fp64 before the sincos so
-// the fp32 path keeps full fp32 accuracy for arguments of many thousands of radians
-// (quadratic phases, OPD / lambda).
-#include "pm_internal.h"
+// All of them are 2-D row-major with a leading dimension.  One thread handles ONE element at a time: a thread owns a column (64
+// adjacent columns per wavefront, so a row is read and written in whole lines) and strides over the rows, 64 x 4 threads per workgroup
+// and at most 65535 workgroups down the rows.  That loop is written once (sweep_kernel); each operation is a named functor with a
+// per-column part and a per-point part.  Phases are reduced in fp64 before the sincos so the fp32 path keeps full fp32 accuracy for
+// arguments of many thousands of radians (quadratic phases, OPD / lambda).
+#include "pm_entry.h"
 
 namespace pm {
 
-static inline dim3 grid2d(int64_t rows, int64_t cols_per_thread_units, dim3& block) {
-    block = dim3(64, 4);
-    int64_t gx = (cols_per_thread_units + block.x - 1) / block.x;
+// ---------------------------------------------------------------- the row sweep
+// F::column(c) is evaluated once per thread (what an operation hoists out of the row loop; NoColumn where there is nothing),
+// F::point(r, c, column) once per element.  More than 4 * 65535 rows are reached by the grid-stride step.
+struct NoColumn {};
+
+template <typename F>
+__global__ void sweep_kernel(int64_t rows, int64_t cols, const F f) {
+    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (c >= cols) return;
+    const auto col = f.column(c);
+    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y) f.point(r, c, col);
+}
+
+template <typename F>
+static int sweep(int64_t rows, int64_t cols, hipStream_t st, const F& f) {
+    const dim3 block(64, 4);
+    const int64_t gx = (cols + block.x - 1) / block.x;
     int64_t gy = (rows + block.y - 1) / block.y;
     if (gy > 65535) gy = 65535;
-    return dim3((unsigned)gx, (unsigned)gy);
+    hipLaunchKernelGGL(sweep_kernel<F>, dim3((unsigned)gx, (unsigned)gy), block, 0, st, rows, cols, f);
+    return int(hipGetLastError());
 }
 
 __device__ __forceinline__ void sincos_turns(double turns, double* s, double* c) {
@@ -25,63 +40,49 @@ __device__ __forceinline__ void sincos_turns(double turns, double* s, double* c)
 
 // ---------------------------------------------------------------- cmul
 template <typename T, int OP>
-__global__ void cmul_kernel(int64_t rows, int64_t cols, const cx<T>* a, int64_t lda, const cx<T>* b, int64_t ldb,
-                            cx<T>* o, int64_t ldo) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y) {
+struct Cmul {
+    const cx<T>* a; int64_t lda; const cx<T>* b; int64_t ldb; cx<T>* o; int64_t ldo;
+    __device__ NoColumn column(int64_t) const { return {}; }
+    __device__ void point(int64_t r, int64_t c, NoColumn) const {
         const cx<T> x = a[r * lda + c], y = b[r * ldb + c];
         o[r * ldo + c] = OP == 0 ? cmul(x, y) : cmulc(x, y);
     }
-}
-
-template <typename T>
-int cmul_launch(int op, int64_t rows, int64_t cols, const void* a, int64_t lda, const void* b, int64_t ldb, void* o,
-                int64_t ldo, hipStream_t st) {
-    dim3 block;
-    dim3 grid = grid2d(rows, cols, block);
-    if (op == 0)
-        hipLaunchKernelGGL((cmul_kernel<T, 0>), grid, block, 0, st, rows, cols, (const cx<T>*)a, lda, (const cx<T>*)b, ldb, (cx<T>*)o, ldo);
-    else
-        hipLaunchKernelGGL((cmul_kernel<T, 1>), grid, block, 0, st, rows, cols, (const cx<T>*)a, lda, (const cx<T>*)b, ldb, (cx<T>*)o, ldo);
-    return int(hipGetLastError());
-}
+};
 
 // ---------------------------------------------------------------- real x complex
 template <typename T>
-__global__ void rmul_kernel(int64_t rows, int64_t cols, const T* r_, int64_t ldr, const cx<T>* a, int64_t lda, T scale,
-                            cx<T>* o, int64_t ldo) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y)
-        o[r * ldo + c] = cscale(a[r * lda + c], scale * r_[r * ldr + c]);
-}
+struct Rmul {
+    const T* r_; int64_t ldr; const cx<T>* a; int64_t lda; T scale; cx<T>* o; int64_t ldo;
+    __device__ NoColumn column(int64_t) const { return {}; }
+    __device__ void point(int64_t r, int64_t c, NoColumn) const { o[r * ldo + c] = cscale(a[r * lda + c], scale * r_[r * ldr + c]); }
+};
 
 // ---------------------------------------------------------------- modulus and phase of one complex array in one sweep
 template <typename T>
-__global__ void abs_arg_kernel(int64_t rows, int64_t cols, const cx<T>* in, int64_t ldi, T* oabs, int64_t lda, T* oarg, int64_t ldg) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y) {
+struct AbsArg {
+    const cx<T>* in; int64_t ldi; T* oabs; int64_t lda; T* oarg; int64_t ldg;
+    __device__ NoColumn column(int64_t) const { return {}; }
+    __device__ void point(int64_t r, int64_t c, NoColumn) const {
         const cx<T> z = in[r * ldi + c];
         if (oabs) oabs[r * lda + c] = sqrt(z.x * z.x + z.y * z.y);
         if (oarg) oarg[r * ldg + c] = atan2(z.y, z.x);
     }
-}
+};
 
 // ---------------------------------------------------------------- separable scale
 template <typename T>
-__global__ void scale_sep_kernel(int64_t rows, int64_t cols, const cx<T>* in, int64_t ldi, const cx<T>* ry, int ryc,
-                                 const cx<T>* cxv, int cxc, T scale, cx<T>* o, int64_t ldo) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    cx<T> fc = {scale, T(0)};
-    if (cxv) {
-        cx<T> w = cxv[c];
-        if (cxc) w.y = -w.y;
-        fc = cscale(w, scale);
+struct ScaleSep {
+    const cx<T>* in; int64_t ldi; const cx<T>* ry; int ryc; const cx<T>* cxv; int cxc; T scale; cx<T>* o; int64_t ldo;
+    __device__ cx<T> column(int64_t c) const {
+        cx<T> fc = {scale, T(0)};
+        if (cxv) {
+            cx<T> w = cxv[c];
+            if (cxc) w.y = -w.y;
+            fc = cscale(w, scale);
+        }
+        return fc;
     }
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y) {
+    __device__ void point(int64_t r, int64_t c, cx<T> fc) const {
         cx<T> f = fc;
         if (ry) {
             cx<T> w = ry[r];
@@ -90,14 +91,14 @@ __global__ void scale_sep_kernel(int64_t rows, int64_t cols, const cx<T>* in, in
         }
         o[r * ldo + c] = cmul(in[r * ldi + c], f);
     }
-}
+};
 
 // ---------------------------------------------------------------- |.|^2
 template <typename T, int ACC>
-__global__ void abs2_kernel(int64_t rows, int64_t cols, const cx<T>* in, int64_t ldi, T* o, int64_t ldo, T weight) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y) {
+struct Abs2 {
+    const cx<T>* in; int64_t ldi; T* o; int64_t ldo; T weight;
+    __device__ NoColumn column(int64_t) const { return {}; }
+    __device__ void point(int64_t r, int64_t c, NoColumn) const {
         const cx<T> x = in[r * ldi + c];
         const T i2 = x.x * x.x + x.y * x.y;
         if (ACC)
@@ -105,7 +106,7 @@ __global__ void abs2_kernel(int64_t rows, int64_t cols, const cx<T>* in, int64_t
         else
             o[r * ldo + c] = i2;
     }
-}
+};
 
 // ---------------------------------------------------------------- weighted sum of modes
 // out (+)= sum_b w[b] * modes[b]; the weights ride in the kernel arguments (SGPRs), 32 modes per launch
@@ -114,35 +115,45 @@ struct ModeWeights {
     T w[32];
 };
 template <typename T>
-__global__ void sum_modes_kernel(int64_t rows, int64_t cols, const T* __restrict__ modes, int64_t mstride, int64_t ldm,
-                                 const ModeWeights<T> mw, int nb, int acc, T* o, int64_t ldo) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y) {
+struct SumModes {
+    const T* __restrict__ modes; int64_t mstride, ldm; ModeWeights<T> mw; int nb, acc; T* o; int64_t ldo;
+    __device__ NoColumn column(int64_t) const { return {}; }
+    __device__ void point(int64_t r, int64_t c, NoColumn) const {
         const T* m = modes + r * ldm + c;
         T a = acc ? o[r * ldo + c] : T(0);
         for (int b = 0; b < nb; ++b) a += mw.w[b] * m[int64_t(b) * mstride];
         o[r * ldo + c] = a;
     }
-}
+};
 
 // ---------------------------------------------------------------- measured focal-plane mask
-// map_coordinates(order 0 | 1, mode='nearest') of a complex map at (row, col) = ((yf-cy)/dx + ny/2, (xf-cx)/dx + nx/2);
-// coordinates are formed in the precision of xf / yf as numpy does, the interpolation itself in fp64 as scipy does.
+// Where output point (r, c) falls in a map of ny x nx samples: (row, col) = ((yf-cy)/dx + ny/2, (xf-cx)/dx + nx/2), formed in the
+// precision of xf / yf as numpy does.  Outside the map the point takes fill[r][c], or fillv where there is no fill array.  Both
+// samplers start here.
 template <typename T>
-__global__ void sample_map_kernel(int order, int64_t ny, int64_t nx, const cx<T>* __restrict__ map, int64_t ldm, T dx, T cxo, T cyo,
-                                  int64_t rows, int64_t cols, const T* xf, int64_t xsy, int64_t xsx, const T* yf, int64_t ysy,
-                                  int64_t ysx, const cx<T>* fill, int64_t ldf, cx<T> fillv, cx<T>* o, int64_t ldo) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y) {
-        const T col = (xf[r * xsy + c * xsx] - cxo) / dx + T(nx / 2);
-        const T row = (yf[r * ysy + c * ysx] - cyo) / dx + T(ny / 2);
+struct SamplePoints {
+    int64_t ny, nx; T dx, cxo, cyo; const T* xf; int64_t xsy, xsx; const T* yf; int64_t ysy, ysx; const cx<T>* fill; int64_t ldf;
+    cx<T> fillv;
+    // true: (row, col) lies inside the map; false: v holds the fill value
+    __device__ __forceinline__ bool locate(int64_t r, int64_t c, T& row, T& col, cx<T>& v) const {
+        col = (xf[r * xsy + c * xsx] - cxo) / dx + T(nx / 2);
+        row = (yf[r * ysy + c * ysx] - cyo) / dx + T(ny / 2);
         const bool inside = row >= T(0) && row <= T(ny - 1) && col >= T(0) && col <= T(nx - 1);
+        if (!inside) v = fill ? fill[r * ldf + c] : fillv;
+        return inside;
+    }
+};
+
+// map_coordinates(order 0 | 1, mode='nearest') of a complex map; the interpolation itself in fp64 as scipy does.
+template <typename T>
+struct SampleMap {
+    int order; const cx<T>* __restrict__ map; int64_t ldm; SamplePoints<T> at; cx<T>* o; int64_t ldo;
+    __device__ NoColumn column(int64_t) const { return {}; }
+    __device__ void point(int64_t r, int64_t c, NoColumn) const {
+        const int64_t ny = at.ny, nx = at.nx;
+        T row, col;
         cx<T> v;
-        if (!inside) {
-            v = fill ? fill[r * ldf + c] : fillv;
-        } else {
+        if (at.locate(r, c, row, col, v)) {
             const double rr = double(row), cc = double(col);
             if (order == 0) {
                 int64_t ir = int64_t(floor(rr + 0.5)), ic = int64_t(floor(cc + 0.5));
@@ -160,7 +171,7 @@ __global__ void sample_map_kernel(int order, int64_t ny, int64_t nx, const cx<T>
         }
         o[r * ldo + c] = v;
     }
-}
+};
 
 // ---------------------------------------------------------------- spline orders 2..5 of map_coordinates(mode='nearest')
 // scipy pads the map by 12 samples of edge values, runs the recursive B-spline prefilter (poles z_k, reflect initialisation, gain
@@ -257,19 +268,13 @@ __device__ __forceinline__ double bspline_value(double t, int n) {
 }
 
 template <typename T>
-__global__ void sample_spline_kernel(int order, int64_t ny, int64_t nx, const cx<double>* __restrict__ coeff, int64_t ldc, T dx, T cxo, T cyo,
-                                     int64_t rows, int64_t cols, const T* xf, int64_t xsy, int64_t xsx, const T* yf, int64_t ysy,
-                                     int64_t ysx, const cx<T>* fill, int64_t ldf, cx<T> fillv, cx<T>* o, int64_t ldo) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y) {
-        const T col = (xf[r * xsy + c * xsx] - cxo) / dx + T(nx / 2);
-        const T row = (yf[r * ysy + c * ysx] - cyo) / dx + T(ny / 2);
-        const bool inside = row >= T(0) && row <= T(ny - 1) && col >= T(0) && col <= T(nx - 1);
+struct SampleSpline {
+    int order; const cx<double>* __restrict__ coeff; int64_t ldc; SamplePoints<T> at; cx<T>* o; int64_t ldo;
+    __device__ NoColumn column(int64_t) const { return {}; }
+    __device__ void point(int64_t r, int64_t c, NoColumn) const {
+        T row, col;
         cx<T> v;
-        if (!inside) {
-            v = fill ? fill[r * ldf + c] : fillv;
-        } else {
+        if (at.locate(r, c, row, col, v)) {
             const double rr = double(row) + kSplinePad, cc = double(col) + kSplinePad;
             const int64_t r0 = int64_t(floor((order & 1) ? rr : rr + 0.5)) - order / 2;
             const int64_t c0 = int64_t(floor((order & 1) ? cc : cc + 0.5)) - order / 2;
@@ -291,35 +296,33 @@ __global__ void sample_spline_kernel(int order, int64_t ny, int64_t nx, const cx
         }
         o[r * ldo + c] = v;
     }
-}
+};
 
 // ---------------------------------------------------------------- pupil synthesis
 template <typename T, typename A>
-__global__ void pupil_kernel(int64_t rows, int64_t cols, const A* amp, int64_t lda, const T* opd, int64_t ldp,
-                             double k_over_2pi, cx<T>* o, int64_t ldo) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y) {
+struct Pupil {
+    const A* amp; int64_t lda; const T* opd; int64_t ldp; double k_over_2pi; cx<T>* o; int64_t ldo;
+    __device__ NoColumn column(int64_t) const { return {}; }
+    __device__ void point(int64_t r, int64_t c, NoColumn) const {
         double s, co;
         sincos_turns(double(opd[r * ldp + c]) * k_over_2pi, &s, &co);
         const double a = amp ? double(amp[r * lda + c]) : 1.0;
         o[r * ldo + c] = {T(a * co), T(a * s)};
     }
-}
+};
 
 template <typename T>
-__global__ void quad_phase_kernel(int64_t rows, int64_t cols, const T* x, int64_t ldx, const T* y, int64_t ldy,
-                                  double c_over_2pi, cx<T>* o, int64_t ldo) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y) {
+struct QuadPhase {
+    const T* x; int64_t ldx; const T* y; int64_t ldy; double c_over_2pi; cx<T>* o; int64_t ldo;
+    __device__ NoColumn column(int64_t) const { return {}; }
+    __device__ void point(int64_t r, int64_t c, NoColumn) const {
         // rsq = x*x + y*y (wavefront.py:139-140), formed in fp64 from the stored coordinates
         const double xv = double(x[r * ldx + c]), yv = double(y[r * ldy + c]);
         double s, co;
         sincos_turns((xv * xv + yv * yv) * c_over_2pi, &s, &co);
         o[r * ldo + c] = {T(co), T(s)};
     }
-}
+};
 
 // ---------------------------------------------------------------- transfer function factors
 // both factors in ONE launch (round 4; two launches cost 9.8 us of config 3's 320): blocks [0, ceil(rows / 256)) fill hy, the rest hx
@@ -342,28 +345,24 @@ __global__ void as_tf_vec_kernel(int64_t rows, int64_t cols, double d, double co
 }
 
 template <typename T>
-__global__ void outer_kernel(int64_t rows, int64_t cols, const cx<T>* hy, const cx<T>* hx, cx<T>* o, int64_t ldo) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    const cx<T> wx = hx[c];
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y)
-        o[r * ldo + c] = cmul(hy[r], wx);
-}
+struct Outer {
+    const cx<T>* hy; const cx<T>* hx; cx<T>* o; int64_t ldo;
+    __device__ cx<T> column(int64_t c) const { return hx[c]; }
+    __device__ void point(int64_t r, int64_t c, cx<T> wx) const { o[r * ldo + c] = cmul(hy[r], wx); }
+};
 
 // ---------------------------------------------------------------- embed (pad / crop)
 template <typename V>
-__global__ void embed_kernel(int64_t irows, int64_t icols, const V* in, int64_t ldi, int64_t orows, int64_t ocols,
-                             int64_t offy, int64_t offx, V fill, V* o, int64_t ldo) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= ocols) return;
-    const int64_t ic = c - offx;
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < orows; r += int64_t(gridDim.y) * blockDim.y) {
+struct Embed {
+    int64_t irows, icols; const V* in; int64_t ldi; int64_t offy, offx; V fill; V* o; int64_t ldo;
+    __device__ int64_t column(int64_t c) const { return c - offx; }
+    __device__ void point(int64_t r, int64_t c, int64_t ic) const {
         const int64_t ir = r - offy;
         V val = fill;
         if (ir >= 0 && ir < irows && ic >= 0 && ic < icols) val = in[ir * ldi + ic];
         o[r * ldo + c] = val;
     }
-}
+};
 
 // np.pad's index-mapping modes (fttools.pad2d(mode=...), prysm/fttools.py:96-98): output index r (relative to the first input
 // sample) reads input index map(r); 1 edge, 2 reflect (period 2n - 2, the edge sample not repeated), 3 symmetric (period 2n), 4 wrap
@@ -382,29 +381,25 @@ __device__ __forceinline__ int64_t pad_map(int64_t r, int64_t n, int mode) {
     return mode == 2 ? period - r : period - 1 - r;
 }
 template <typename V>
-__global__ void pad_index_kernel(int mode, int64_t irows, int64_t icols, const V* in, int64_t ldi, int64_t orows, int64_t ocols,
-                                 int64_t offy, int64_t offx, V* o, int64_t ldo) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= ocols) return;
-    const int64_t ic = pad_map(c - offx, icols, mode);
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < orows; r += int64_t(gridDim.y) * blockDim.y)
-        o[r * ldo + c] = in[pad_map(r - offy, irows, mode) * ldi + ic];
-}
+struct PadIndex {
+    int mode; int64_t irows, icols; const V* in; int64_t ldi; int64_t offy, offx; V* o; int64_t ldo;
+    __device__ int64_t column(int64_t c) const { return pad_map(c - offx, icols, mode); }
+    __device__ void point(int64_t r, int64_t c, int64_t ic) const { o[r * ldo + c] = in[pad_map(r - offy, irows, mode) * ldi + ic]; }
+};
 
 // ---------------------------------------------------------------- MDFT basis
 template <typename T>
-__global__ void mdft_basis_kernel(int64_t M, int64_t N, const T* f, const T* x, double sign, cx<T>* E, int64_t ldE) {
-    const int64_t n = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (n >= N) return;
-    const double xv = double(x[n]);
-    for (int64_t m = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; m < M; m += int64_t(gridDim.y) * blockDim.y) {
+struct MdftBasis {
+    const T* f; const T* x; double sign; cx<T>* E; int64_t ldE;
+    __device__ double column(int64_t n) const { return double(x[n]); }
+    __device__ void point(int64_t m, int64_t n, double xv) const {
         // exp(sign 2 pi i outer(f, x)) (fttools.py:189-191); the product and its reduction to one turn
         // are done in fp64 so the fp32 basis carries a single rounding
         double s, co;
         sincos_turns(sign * double(f[m]) * xv, &s, &co);
         E[m * ldE + n] = {T(co), T(s)};
     }
-}
+};
 
 // ---------------------------------------------------------------- chirp-Z vectors
 // The three chirps of one CZT axis (prysm/fttools.py:364-389 _prepare_czt_basis) from its scalars, one launch: input chirp
@@ -449,31 +444,20 @@ template <typename T> __device__ __forceinline__ T add_rn(T a, T b) {
 // the same basis with both vectors given as FFT-centred grids, built in the kernel exactly as coordinates_for_focus builds them:
 //   x[n] = (n - N/2) * x_step,   f[m] = ((m - M/2) * f_step + f_shift) * f_scale,   every operation rounded in T
 template <typename T>
-__global__ void mdft_basis_grid_kernel(int64_t M, int64_t N, T f_step, T f_shift, T f_scale, T x_step, double sign, cx<T>* E, int64_t ldE) {
-    const int64_t n = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (n >= N) return;
-    const double xv = double(mul_rn(T(n - N / 2), x_step));
-    for (int64_t m = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; m < M; m += int64_t(gridDim.y) * blockDim.y) {
+struct MdftBasisGrid {
+    int64_t M, N; T f_step, f_shift, f_scale, x_step; double sign; cx<T>* E; int64_t ldE;
+    __device__ double column(int64_t n) const { return double(mul_rn(T(n - N / 2), x_step)); }
+    __device__ void point(int64_t m, int64_t n, double xv) const {
         const T fv = mul_rn(add_rn(mul_rn(T(m - M / 2), f_step), f_shift), f_scale);
         double s, co;
         sincos_turns(sign * double(fv) * xv, &s, &co);
         E[m * ldE + n] = {T(co), T(s)};
     }
-}
+};
 
 }  // namespace pm
 
 using namespace pm;
-
-#define PM_STREAM(s) reinterpret_cast<hipStream_t>(s)
-
-// rows of a rows x cols window lie `ld` elements apart: with more than one row a leading dimension below cols would make rows overlap
-// (and an output race); one row takes any value (the wrappers pass the length there)
-static inline bool ld_ok(int64_t rows, int64_t cols, int64_t ld) { return rows <= 1 || ld >= cols; }
-#define PM_CHECK_LD(name, cond)                                                                                        \
-    do {                                                                                                               \
-        if (!(cond)) return fail(PM_ERR_ARG, name ": a leading dimension is smaller than the number of columns");      \
-    } while (0)
 
 // ---------------------------------------------------------------- real-input 2-D spectrum from the transform of the packed array
 // A real M x N array (N even) read as M x N/2 complex numbers z[r][j] = x[r][2j] + i x[r][2j+1] costs nothing to form -- it is the same
@@ -603,11 +587,10 @@ int pm_r2c_untangle(int32_t dtype, int64_t M, int64_t N, const void* zf, int64_t
     if (in_shift_y < 0 || in_shift_y >= M || in_shift_x < 0 || in_shift_x >= N || out_shift_y < 0 || out_shift_y >= M || out_shift_x < 0 ||
         out_shift_x >= N)
         return fail(PM_ERR_ARG, "pm_r2c_untangle: shifts must lie in [0, length)");
-    if (dtype == PM_C64)
-        return r2c_untangle_launch<float>(M, N, zf, zf_ld, in_shift_y, in_shift_x, out_shift_y, out_shift_x, epilogue, norm_dc, scale, out, out_ld, PM_STREAM(stream));
-    if (dtype == PM_C128)
-        return r2c_untangle_launch<double>(M, N, zf, zf_ld, in_shift_y, in_shift_x, out_shift_y, out_shift_x, epilogue, norm_dc, scale, out, out_ld, PM_STREAM(stream));
-    return fail(PM_ERR_ARG, "pm_r2c_untangle: dtype must be PM_C64 or PM_C128");
+    return by_cdtype(dtype, "pm_r2c_untangle", [&](auto real) {
+        return r2c_untangle_launch<decltype(real)>(M, N, zf, zf_ld, in_shift_y, in_shift_x, out_shift_y, out_shift_x, epilogue, norm_dc, scale, out,
+                                                   out_ld, PM_STREAM(stream));
+    });
 }
 
 int pm_cmul(int32_t dtype, int32_t op, int64_t rows, int64_t cols, const void* a, int64_t a_ld, const void* b,
@@ -615,9 +598,14 @@ int pm_cmul(int32_t dtype, int32_t op, int64_t rows, int64_t cols, const void* a
     if (!a || !b || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_cmul: bad argument");
     PM_CHECK_LD("pm_cmul", ld_ok(rows, cols, a_ld) && ld_ok(rows, cols, b_ld) && ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
-    if (dtype == PM_C64) return cmul_launch<float>(op, rows, cols, a, a_ld, b, b_ld, out, out_ld, PM_STREAM(stream));
-    if (dtype == PM_C128) return cmul_launch<double>(op, rows, cols, a, a_ld, b, b_ld, out, out_ld, PM_STREAM(stream));
-    return fail(PM_ERR_ARG, "pm_cmul: dtype must be PM_C64 or PM_C128");
+    return by_cdtype(dtype, "pm_cmul", [&](auto real) {
+        using T = decltype(real);
+        const auto go = [&](auto f) {
+            f = {(const cx<T>*)a, a_ld, (const cx<T>*)b, b_ld, (cx<T>*)out, out_ld};
+            return sweep(rows, cols, PM_STREAM(stream), f);
+        };
+        return op == 0 ? go(Cmul<T, 0>{}) : go(Cmul<T, 1>{});
+    });
 }
 
 int pm_rmul(int32_t dtype, int64_t rows, int64_t cols, const void* r, int64_t r_ld, const void* a, int64_t a_ld, double scale,
@@ -625,17 +613,10 @@ int pm_rmul(int32_t dtype, int64_t rows, int64_t cols, const void* r, int64_t r_
     if (!r || !a || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_rmul: bad argument");
     PM_CHECK_LD("pm_rmul", ld_ok(rows, cols, r_ld) && ld_ok(rows, cols, a_ld) && ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(rows, cols, block);
-    if (dtype == PM_C64)
-        hipLaunchKernelGGL(rmul_kernel<float>, grid, block, 0, PM_STREAM(stream), rows, cols, (const float*)r, r_ld, (const cx<float>*)a,
-                           a_ld, float(scale), (cx<float>*)out, out_ld);
-    else if (dtype == PM_C128)
-        hipLaunchKernelGGL(rmul_kernel<double>, grid, block, 0, PM_STREAM(stream), rows, cols, (const double*)r, r_ld,
-                           (const cx<double>*)a, a_ld, scale, (cx<double>*)out, out_ld);
-    else
-        return fail(PM_ERR_ARG, "pm_rmul: dtype must be PM_C64 or PM_C128");
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_rmul", [&](auto real) {
+        using T = decltype(real);
+        return sweep(rows, cols, PM_STREAM(stream), Rmul<T>{(const T*)r, r_ld, (const cx<T>*)a, a_ld, T(scale), (cx<T>*)out, out_ld});
+    });
 }
 
 int pm_scale_sep(int32_t dtype, int64_t rows, int64_t cols, const void* in, int64_t in_ld, const void* ry,
@@ -644,17 +625,11 @@ int pm_scale_sep(int32_t dtype, int64_t rows, int64_t cols, const void* in, int6
     if (!in || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_scale_sep: bad argument");
     PM_CHECK_LD("pm_scale_sep", ld_ok(rows, cols, in_ld) && ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(rows, cols, block);
-    if (dtype == PM_C64)
-        hipLaunchKernelGGL(scale_sep_kernel<float>, grid, block, 0, PM_STREAM(stream), rows, cols, (const cx<float>*)in, in_ld,
-                           (const cx<float>*)ry, ry_conj, (const cx<float>*)cxv, cx_conj, float(scale), (cx<float>*)out, out_ld);
-    else if (dtype == PM_C128)
-        hipLaunchKernelGGL(scale_sep_kernel<double>, grid, block, 0, PM_STREAM(stream), rows, cols, (const cx<double>*)in, in_ld,
-                           (const cx<double>*)ry, ry_conj, (const cx<double>*)cxv, cx_conj, scale, (cx<double>*)out, out_ld);
-    else
-        return fail(PM_ERR_ARG, "pm_scale_sep: dtype must be PM_C64 or PM_C128");
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_scale_sep", [&](auto real) {
+        using T = decltype(real);
+        return sweep(rows, cols, PM_STREAM(stream),
+                     ScaleSep<T>{(const cx<T>*)in, in_ld, (const cx<T>*)ry, ry_conj, (const cx<T>*)cxv, cx_conj, T(scale), (cx<T>*)out, out_ld});
+    });
 }
 
 int pm_abs2(int32_t dtype, int64_t rows, int64_t cols, const void* in, int64_t in_ld, void* out, int64_t out_ld,
@@ -662,22 +637,14 @@ int pm_abs2(int32_t dtype, int64_t rows, int64_t cols, const void* in, int64_t i
     if (!in || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_abs2: bad argument");
     PM_CHECK_LD("pm_abs2", ld_ok(rows, cols, in_ld) && ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(rows, cols, block);
-    hipStream_t st = PM_STREAM(stream);
-    if (dtype == PM_C64) {
-        if (accumulate)
-            hipLaunchKernelGGL((abs2_kernel<float, 1>), grid, block, 0, st, rows, cols, (const cx<float>*)in, in_ld, (float*)out, out_ld, float(weight));
-        else
-            hipLaunchKernelGGL((abs2_kernel<float, 0>), grid, block, 0, st, rows, cols, (const cx<float>*)in, in_ld, (float*)out, out_ld, 1.f);
-    } else if (dtype == PM_C128) {
-        if (accumulate)
-            hipLaunchKernelGGL((abs2_kernel<double, 1>), grid, block, 0, st, rows, cols, (const cx<double>*)in, in_ld, (double*)out, out_ld, weight);
-        else
-            hipLaunchKernelGGL((abs2_kernel<double, 0>), grid, block, 0, st, rows, cols, (const cx<double>*)in, in_ld, (double*)out, out_ld, 1.0);
-    } else
-        return fail(PM_ERR_ARG, "pm_abs2: dtype must be PM_C64 or PM_C128");
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_abs2", [&](auto real) {
+        using T = decltype(real);
+        const auto go = [&](auto f) {
+            f = {(const cx<T>*)in, in_ld, (T*)out, out_ld, accumulate ? T(weight) : T(1)};      // the weight is applied only when accumulating
+            return sweep(rows, cols, PM_STREAM(stream), f);
+        };
+        return accumulate ? go(Abs2<T, 1>{}) : go(Abs2<T, 0>{});
+    });
 }
 
 int pm_abs_arg(int32_t dtype, int64_t rows, int64_t cols, const void* in, int64_t in_ld, void* out_abs, int64_t abs_ld, void* out_arg,
@@ -685,48 +652,35 @@ int pm_abs_arg(int32_t dtype, int64_t rows, int64_t cols, const void* in, int64_
     if (!in || (!out_abs && !out_arg) || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_abs_arg: bad argument");
     PM_CHECK_LD("pm_abs_arg", ld_ok(rows, cols, in_ld) && (!out_abs || ld_ok(rows, cols, abs_ld)) && (!out_arg || ld_ok(rows, cols, arg_ld)));
     if (rows == 0 || cols == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(rows, cols, block);
-    if (dtype == PM_C64)
-        hipLaunchKernelGGL(abs_arg_kernel<float>, grid, block, 0, PM_STREAM(stream), rows, cols, (const cx<float>*)in, in_ld, (float*)out_abs,
-                           abs_ld, (float*)out_arg, arg_ld);
-    else if (dtype == PM_C128)
-        hipLaunchKernelGGL(abs_arg_kernel<double>, grid, block, 0, PM_STREAM(stream), rows, cols, (const cx<double>*)in, in_ld,
-                           (double*)out_abs, abs_ld, (double*)out_arg, arg_ld);
-    else
-        return fail(PM_ERR_ARG, "pm_abs_arg: dtype must be PM_C64 or PM_C128");
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_abs_arg", [&](auto real) {
+        using T = decltype(real);
+        return sweep(rows, cols, PM_STREAM(stream), AbsArg<T>{(const cx<T>*)in, in_ld, (T*)out_abs, abs_ld, (T*)out_arg, arg_ld});
+    });
 }
 
 int pm_sum_modes(int32_t dtype, int64_t nmodes, int64_t rows, int64_t cols, const void* modes, int64_t mode_stride,
                  int64_t modes_ld, const double* weights, int32_t accumulate, void* out, int64_t out_ld, void* stream) {
     if (!modes || !out || (!weights && nmodes > 0) || rows < 0 || cols < 0 || nmodes < 0) return fail(PM_ERR_ARG, "pm_sum_modes: bad argument");
     PM_CHECK_LD("pm_sum_modes", ld_ok(rows, cols, modes_ld) && ld_ok(rows, cols, out_ld));
+    // unlike its neighbours this entry point refuses a bad dtype BEFORE the empty-shape return
     if (dtype != PM_C64 && dtype != PM_C128) return fail(PM_ERR_ARG, "pm_sum_modes: dtype must be PM_C64 (float images) or PM_C128 (double)");
     if (rows == 0 || cols == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(rows, cols, block);
-    hipStream_t st = PM_STREAM(stream);
-    int acc = accumulate ? 1 : 0;
-    if (nmodes == 0 && acc) return 0;
-    int64_t b0 = 0;
-    do {   // 32 modes per launch; an empty sum still writes zeros
-        const int nb = int(nmodes - b0 < 32 ? nmodes - b0 : 32);
-        if (dtype == PM_C64) {
-            ModeWeights<float> mw;
-            for (int i = 0; i < 32; ++i) mw.w[i] = i < nb ? float(weights[b0 + i]) : 0.f;
-            hipLaunchKernelGGL(sum_modes_kernel<float>, grid, block, 0, st, rows, cols, (const float*)modes + b0 * mode_stride, mode_stride,
-                               modes_ld, mw, nb, acc, (float*)out, out_ld);
-        } else {
-            ModeWeights<double> mw;
-            for (int i = 0; i < 32; ++i) mw.w[i] = i < nb ? weights[b0 + i] : 0.0;
-            hipLaunchKernelGGL(sum_modes_kernel<double>, grid, block, 0, st, rows, cols, (const double*)modes + b0 * mode_stride,
-                               mode_stride, modes_ld, mw, nb, acc, (double*)out, out_ld);
-        }
-        acc = 1;
-        b0 += 32;
-    } while (b0 < nmodes);
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_sum_modes", [&](auto real) {
+        using T = decltype(real);
+        int acc = accumulate ? 1 : 0;
+        if (nmodes == 0 && acc) return 0;
+        int rc = 0;
+        int64_t b0 = 0;
+        do {   // 32 modes per launch; an empty sum still writes zeros
+            const int nb = int(nmodes - b0 < 32 ? nmodes - b0 : 32);
+            ModeWeights<T> mw;
+            for (int i = 0; i < 32; ++i) mw.w[i] = i < nb ? T(weights[b0 + i]) : T(0);
+            rc = sweep(rows, cols, PM_STREAM(stream), SumModes<T>{(const T*)modes + b0 * mode_stride, mode_stride, modes_ld, mw, nb, acc, (T*)out, out_ld});
+            acc = 1;
+            b0 += 32;
+        } while (rc == 0 && b0 < nmodes);
+        return rc;
+    });
 }
 
 int pm_sample_map(int32_t dtype, int32_t order, int64_t map_rows, int64_t map_cols, const void* map, int64_t map_ld, double dx,
@@ -738,20 +692,12 @@ int pm_sample_map(int32_t dtype, int32_t order, int64_t map_rows, int64_t map_co
     PM_CHECK_LD("pm_sample_map", ld_ok(map_rows, map_cols, map_ld) && (!fill || ld_ok(rows, cols, fill_ld)) && ld_ok(rows, cols, out_ld));
     if (order != 0 && order != 1) return fail(PM_ERR_UNSUPPORTED, "pm_sample_map: spline order must be 0 or 1");
     if (rows == 0 || cols == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(rows, cols, block);
-    hipStream_t st = PM_STREAM(stream);
-    if (dtype == PM_C64)
-        hipLaunchKernelGGL(sample_map_kernel<float>, grid, block, 0, st, order, map_rows, map_cols, (const cx<float>*)map, map_ld, float(dx),
-                           float(center_x), float(center_y), rows, cols, (const float*)xf, xf_sy, xf_sx, (const float*)yf, yf_sy, yf_sx,
-                           (const cx<float>*)fill, fill_ld, cx<float>{float(fill_re), float(fill_im)}, (cx<float>*)out, out_ld);
-    else if (dtype == PM_C128)
-        hipLaunchKernelGGL(sample_map_kernel<double>, grid, block, 0, st, order, map_rows, map_cols, (const cx<double>*)map, map_ld, dx,
-                           center_x, center_y, rows, cols, (const double*)xf, xf_sy, xf_sx, (const double*)yf, yf_sy, yf_sx,
-                           (const cx<double>*)fill, fill_ld, cx<double>{fill_re, fill_im}, (cx<double>*)out, out_ld);
-    else
-        return fail(PM_ERR_ARG, "pm_sample_map: dtype must be PM_C64 or PM_C128");
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_sample_map", [&](auto real) {
+        using T = decltype(real);
+        const SamplePoints<T> at{map_rows, map_cols, T(dx), T(center_x), T(center_y), (const T*)xf, xf_sy, xf_sx, (const T*)yf, yf_sy, yf_sx,
+                                 (const cx<T>*)fill, fill_ld, cx<T>{T(fill_re), T(fill_im)}};
+        return sweep(rows, cols, PM_STREAM(stream), SampleMap<T>{order, (const cx<T>*)map, map_ld, at, (cx<T>*)out, out_ld});
+    });
 }
 
 int pm_spline_prefilter(int32_t dtype, int32_t order, int64_t map_rows, int64_t map_cols, const void* map, int64_t map_ld, void* coeff,
@@ -759,22 +705,20 @@ int pm_spline_prefilter(int32_t dtype, int32_t order, int64_t map_rows, int64_t 
     if (!map || !coeff || map_rows < 1 || map_cols < 1 || map_ld < map_cols || coeff_ld < map_cols + 2 * kSplinePad)
         return fail(PM_ERR_ARG, "pm_spline_prefilter: bad argument");
     if (order < 2 || order > 5) return fail(PM_ERR_UNSUPPORTED, "pm_spline_prefilter: spline order must be 2 .. 5 (orders 0 and 1 need no prefilter)");
-    if (dtype != PM_C64 && dtype != PM_C128) return fail(PM_ERR_ARG, "pm_spline_prefilter: dtype must be PM_C64 or PM_C128");
-    hipStream_t st = PM_STREAM(stream);
-    const SplinePoles pl = spline_poles(order);
-    double gain = 1.0;
-    for (int k = 0; k < pl.n; ++k) gain *= (1.0 - pl.z[k]) * (1.0 - 1.0 / pl.z[k]);
-    const int64_t py = map_rows + 2 * kSplinePad, px = map_cols + 2 * kSplinePad;
-    const dim3 block(256), grid(unsigned((py * px + 255) / 256));
-    if (dtype == PM_C64)
-        hipLaunchKernelGGL(spline_pad_kernel<float>, grid, block, 0, st, map_rows, map_cols, (const cx<float>*)map, map_ld, gain * gain,
-                           (cx<double>*)coeff, coeff_ld);
-    else
-        hipLaunchKernelGGL(spline_pad_kernel<double>, grid, block, 0, st, map_rows, map_cols, (const cx<double>*)map, map_ld, gain * gain,
-                           (cx<double>*)coeff, coeff_ld);
-    hipLaunchKernelGGL(spline_filter_kernel, dim3(unsigned((px + 63) / 64)), dim3(64), 0, st, 0, py, px, (cx<double>*)coeff, coeff_ld, pl);
-    hipLaunchKernelGGL(spline_filter_kernel, dim3(unsigned((py + 63) / 64)), dim3(64), 0, st, 1, py, px, (cx<double>*)coeff, coeff_ld, pl);
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_spline_prefilter", [&](auto real) {
+        using T = decltype(real);
+        hipStream_t st = PM_STREAM(stream);
+        const SplinePoles pl = spline_poles(order);
+        double gain = 1.0;
+        for (int k = 0; k < pl.n; ++k) gain *= (1.0 - pl.z[k]) * (1.0 - 1.0 / pl.z[k]);
+        const int64_t py = map_rows + 2 * kSplinePad, px = map_cols + 2 * kSplinePad;
+        const dim3 block(256), grid(unsigned((py * px + 255) / 256));
+        hipLaunchKernelGGL(spline_pad_kernel<T>, grid, block, 0, st, map_rows, map_cols, (const cx<T>*)map, map_ld, gain * gain, (cx<double>*)coeff,
+                           coeff_ld);
+        hipLaunchKernelGGL(spline_filter_kernel, dim3(unsigned((px + 63) / 64)), dim3(64), 0, st, 0, py, px, (cx<double>*)coeff, coeff_ld, pl);
+        hipLaunchKernelGGL(spline_filter_kernel, dim3(unsigned((py + 63) / 64)), dim3(64), 0, st, 1, py, px, (cx<double>*)coeff, coeff_ld, pl);
+        return int(hipGetLastError());
+    });
 }
 
 int pm_sample_spline(int32_t dtype, int32_t order, int64_t map_rows, int64_t map_cols, const void* coeff, int64_t coeff_ld, double dx,
@@ -787,20 +731,12 @@ int pm_sample_spline(int32_t dtype, int32_t order, int64_t map_rows, int64_t map
     PM_CHECK_LD("pm_sample_spline", (!fill || ld_ok(rows, cols, fill_ld)) && ld_ok(rows, cols, out_ld));
     if (order < 2 || order > 5) return fail(PM_ERR_UNSUPPORTED, "pm_sample_spline: spline order must be 2 .. 5 (pm_sample_map serves 0 and 1)");
     if (rows == 0 || cols == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(rows, cols, block);
-    hipStream_t st = PM_STREAM(stream);
-    if (dtype == PM_C64)
-        hipLaunchKernelGGL(sample_spline_kernel<float>, grid, block, 0, st, order, map_rows, map_cols, (const cx<double>*)coeff, coeff_ld,
-                           float(dx), float(center_x), float(center_y), rows, cols, (const float*)xf, xf_sy, xf_sx, (const float*)yf, yf_sy,
-                           yf_sx, (const cx<float>*)fill, fill_ld, cx<float>{float(fill_re), float(fill_im)}, (cx<float>*)out, out_ld);
-    else if (dtype == PM_C128)
-        hipLaunchKernelGGL(sample_spline_kernel<double>, grid, block, 0, st, order, map_rows, map_cols, (const cx<double>*)coeff, coeff_ld, dx,
-                           center_x, center_y, rows, cols, (const double*)xf, xf_sy, xf_sx, (const double*)yf, yf_sy, yf_sx,
-                           (const cx<double>*)fill, fill_ld, cx<double>{fill_re, fill_im}, (cx<double>*)out, out_ld);
-    else
-        return fail(PM_ERR_ARG, "pm_sample_spline: dtype must be PM_C64 or PM_C128");
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_sample_spline", [&](auto real) {
+        using T = decltype(real);
+        const SamplePoints<T> at{map_rows, map_cols, T(dx), T(center_x), T(center_y), (const T*)xf, xf_sy, xf_sx, (const T*)yf, yf_sy, yf_sx,
+                                 (const cx<T>*)fill, fill_ld, cx<T>{T(fill_re), T(fill_im)}};
+        return sweep(rows, cols, PM_STREAM(stream), SampleSpline<T>{order, (const cx<double>*)coeff, coeff_ld, at, (cx<T>*)out, out_ld});
+    });
 }
 
 int pm_pupil_synth(int32_t dtype, int64_t rows, int64_t cols, const void* amp, int32_t amp_dtype, int64_t amp_ld,
@@ -808,26 +744,21 @@ int pm_pupil_synth(int32_t dtype, int64_t rows, int64_t cols, const void* amp, i
     if (!opd || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_pupil_synth: bad argument");
     PM_CHECK_LD("pm_pupil_synth", (!amp || ld_ok(rows, cols, amp_ld)) && ld_ok(rows, cols, opd_ld) && ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(rows, cols, block);
-    hipStream_t st = PM_STREAM(stream);
     const double k2 = k / (2.0 * 3.14159265358979323846264338327950288);
-#define PM_PUPIL(T, A) \
-    hipLaunchKernelGGL((pupil_kernel<T, A>), grid, block, 0, st, rows, cols, (const A*)amp, amp_ld, (const T*)opd, opd_ld, k2, (cx<T>*)out, out_ld)
-    if (dtype == PM_C64) {
-        if (!amp || amp_dtype == PM_F32) PM_PUPIL(float, float);
-        else if (amp_dtype == PM_F64) PM_PUPIL(float, double);
-        else if (amp_dtype == PM_BOOL) PM_PUPIL(float, unsigned char);
-        else return fail(PM_ERR_ARG, "pm_pupil_synth: amp_dtype");
-    } else if (dtype == PM_C128) {
-        if (!amp || amp_dtype == PM_F64) PM_PUPIL(double, double);
-        else if (amp_dtype == PM_F32) PM_PUPIL(double, float);
-        else if (amp_dtype == PM_BOOL) PM_PUPIL(double, unsigned char);
-        else return fail(PM_ERR_ARG, "pm_pupil_synth: amp_dtype");
-    } else
-        return fail(PM_ERR_ARG, "pm_pupil_synth: dtype must be PM_C64 or PM_C128");
-#undef PM_PUPIL
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_pupil_synth", [&](auto real) {
+        using T = decltype(real);
+        const auto with_amp = [&](auto a) {
+            using A = decltype(a);
+            return sweep(rows, cols, PM_STREAM(stream), Pupil<T, A>{(const A*)amp, amp_ld, (const T*)opd, opd_ld, k2, (cx<T>*)out, out_ld});
+        };
+        if (!amp) return with_amp(T{});      // no amplitude: its type is not looked at
+        switch (amp_dtype) {
+            case PM_F32: return with_amp(float{});
+            case PM_F64: return with_amp(double{});
+            case PM_BOOL: return with_amp((unsigned char)0);
+        }
+        return fail(PM_ERR_ARG, "pm_pupil_synth: amp_dtype");
+    });
 }
 
 int pm_quadratic_phase(int32_t dtype, int64_t rows, int64_t cols, const void* x, int64_t x_ld, const void* y,
@@ -835,16 +766,11 @@ int pm_quadratic_phase(int32_t dtype, int64_t rows, int64_t cols, const void* x,
     if (!x || !y || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_quadratic_phase: bad argument");
     PM_CHECK_LD("pm_quadratic_phase", ld_ok(rows, cols, x_ld) && ld_ok(rows, cols, y_ld) && ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(rows, cols, block);
     const double c2 = c / (2.0 * 3.14159265358979323846264338327950288);
-    if (dtype == PM_C64)
-        hipLaunchKernelGGL(quad_phase_kernel<float>, grid, block, 0, PM_STREAM(stream), rows, cols, (const float*)x, x_ld, (const float*)y, y_ld, c2, (cx<float>*)out, out_ld);
-    else if (dtype == PM_C128)
-        hipLaunchKernelGGL(quad_phase_kernel<double>, grid, block, 0, PM_STREAM(stream), rows, cols, (const double*)x, x_ld, (const double*)y, y_ld, c2, (cx<double>*)out, out_ld);
-    else
-        return fail(PM_ERR_ARG, "pm_quadratic_phase: dtype must be PM_C64 or PM_C128");
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_quadratic_phase", [&](auto real) {
+        using T = decltype(real);
+        return sweep(rows, cols, PM_STREAM(stream), QuadPhase<T>{(const T*)x, x_ld, (const T*)y, y_ld, c2, (cx<T>*)out, out_ld});
+    });
 }
 
 int pm_as_tf_vectors(int32_t dtype, int64_t rows, int64_t cols, double wvl_um, double dx, double z, void* hy, void* hx,
@@ -852,15 +778,12 @@ int pm_as_tf_vectors(int32_t dtype, int64_t rows, int64_t cols, double wvl_um, d
     if (!hy || !hx || rows <= 0 || cols <= 0) return fail(PM_ERR_ARG, "pm_as_tf_vectors: bad argument");
     // exp(-i pi (wvl/1e3) z k^2) = exp(2 pi i * (-(wvl/1e3) z / 2) k^2)
     const double coef = -(wvl_um / 1e3) * z * 0.5;
-    hipStream_t st = PM_STREAM(stream);
     const unsigned blocks = unsigned((rows + 255) / 256 + (cols + 255) / 256);
-    if (dtype == PM_C64) {
-        hipLaunchKernelGGL(as_tf_vec_kernel<float>, dim3(blocks), dim3(256), 0, st, rows, cols, dx, coef, (cx<float>*)hy, (cx<float>*)hx);
-    } else if (dtype == PM_C128) {
-        hipLaunchKernelGGL(as_tf_vec_kernel<double>, dim3(blocks), dim3(256), 0, st, rows, cols, dx, coef, (cx<double>*)hy, (cx<double>*)hx);
-    } else
-        return fail(PM_ERR_ARG, "pm_as_tf_vectors: dtype must be PM_C64 or PM_C128");
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_as_tf_vectors", [&](auto real) {
+        using T = decltype(real);
+        hipLaunchKernelGGL(as_tf_vec_kernel<T>, dim3(blocks), dim3(256), 0, PM_STREAM(stream), rows, cols, dx, coef, (cx<T>*)hy, (cx<T>*)hx);
+        return int(hipGetLastError());
+    });
 }
 
 int pm_outer(int32_t dtype, int64_t rows, int64_t cols, const void* hy, const void* hx, void* out, int64_t out_ld,
@@ -868,15 +791,10 @@ int pm_outer(int32_t dtype, int64_t rows, int64_t cols, const void* hy, const vo
     if (!hy || !hx || !out || rows < 0 || cols < 0) return fail(PM_ERR_ARG, "pm_outer: bad argument");
     PM_CHECK_LD("pm_outer", ld_ok(rows, cols, out_ld));
     if (rows == 0 || cols == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(rows, cols, block);
-    if (dtype == PM_C64)
-        hipLaunchKernelGGL(outer_kernel<float>, grid, block, 0, PM_STREAM(stream), rows, cols, (const cx<float>*)hy, (const cx<float>*)hx, (cx<float>*)out, out_ld);
-    else if (dtype == PM_C128)
-        hipLaunchKernelGGL(outer_kernel<double>, grid, block, 0, PM_STREAM(stream), rows, cols, (const cx<double>*)hy, (const cx<double>*)hx, (cx<double>*)out, out_ld);
-    else
-        return fail(PM_ERR_ARG, "pm_outer: dtype must be PM_C64 or PM_C128");
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_outer", [&](auto real) {
+        using T = decltype(real);
+        return sweep(rows, cols, PM_STREAM(stream), Outer<T>{(const cx<T>*)hy, (const cx<T>*)hx, (cx<T>*)out, out_ld});
+    });
 }
 
 int pm_embed(int32_t elem_bytes, int64_t irows, int64_t icols, const void* in, int64_t in_ld, int64_t orows,
@@ -884,25 +802,12 @@ int pm_embed(int32_t elem_bytes, int64_t irows, int64_t icols, const void* in, i
     if (!in || !out || irows < 0 || icols < 0 || orows < 0 || ocols < 0) return fail(PM_ERR_ARG, "pm_embed: bad argument");
     PM_CHECK_LD("pm_embed", ld_ok(irows, icols, in_ld) && ld_ok(orows, ocols, out_ld));
     if (orows == 0 || ocols == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(orows, ocols, block);
-    hipStream_t st = PM_STREAM(stream);
-#define PM_EMBED(V)                                                                                              \
-    {                                                                                                            \
-        V f{};                                                                                                   \
-        if (fill) f = *reinterpret_cast<const V*>(fill);                                                         \
-        hipLaunchKernelGGL(embed_kernel<V>, grid, block, 0, st, irows, icols, (const V*)in, in_ld, orows, ocols, \
-                           off_y, off_x, f, (V*)out, out_ld);                                                    \
-    }
-    switch (elem_bytes) {
-        case 1: PM_EMBED(unsigned char) break;
-        case 4: PM_EMBED(float) break;
-        case 8: PM_EMBED(double) break;
-        case 16: PM_EMBED(double2) break;
-        default: return fail(PM_ERR_ARG, "pm_embed: elem_bytes must be 1, 4, 8 or 16");
-    }
-#undef PM_EMBED
-    return int(hipGetLastError());
+    return by_elem_bytes(elem_bytes, "pm_embed", [&](auto elem) {
+        using V = decltype(elem);
+        V f{};
+        if (fill) f = *reinterpret_cast<const V*>(fill);
+        return sweep(orows, ocols, PM_STREAM(stream), Embed<V>{irows, icols, (const V*)in, in_ld, off_y, off_x, f, (V*)out, out_ld});
+    });
 }
 
 int pm_pad_index(int32_t elem_bytes, int32_t mode, int64_t irows, int64_t icols, const void* in, int64_t in_ld, int64_t orows,
@@ -911,20 +816,10 @@ int pm_pad_index(int32_t elem_bytes, int32_t mode, int64_t irows, int64_t icols,
         return fail(PM_ERR_ARG, "pm_pad_index: bad argument");
     PM_CHECK_LD("pm_pad_index", ld_ok(irows, icols, in_ld) && ld_ok(orows, ocols, out_ld));
     if (orows == 0 || ocols == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(orows, ocols, block);
-    hipStream_t st = PM_STREAM(stream);
-#define PM_PADI(V) \
-    hipLaunchKernelGGL(pad_index_kernel<V>, grid, block, 0, st, mode, irows, icols, (const V*)in, in_ld, orows, ocols, off_y, off_x, (V*)out, out_ld)
-    switch (elem_bytes) {
-        case 1: PM_PADI(unsigned char); break;
-        case 4: PM_PADI(float); break;
-        case 8: PM_PADI(double); break;
-        case 16: PM_PADI(double2); break;
-        default: return fail(PM_ERR_ARG, "pm_pad_index: elem_bytes must be 1, 4, 8 or 16");
-    }
-#undef PM_PADI
-    return int(hipGetLastError());
+    return by_elem_bytes(elem_bytes, "pm_pad_index", [&](auto elem) {
+        using V = decltype(elem);
+        return sweep(orows, ocols, PM_STREAM(stream), PadIndex<V>{mode, irows, icols, (const V*)in, in_ld, off_y, off_x, (V*)out, out_ld});
+    });
 }
 
 int pm_mdft_basis(int32_t dtype, int64_t M, int64_t N, const void* f, const void* x, int32_t sign, void* E,
@@ -932,15 +827,10 @@ int pm_mdft_basis(int32_t dtype, int64_t M, int64_t N, const void* f, const void
     if (!f || !x || !E || M < 0 || N < 0 || (sign != 1 && sign != -1)) return fail(PM_ERR_ARG, "pm_mdft_basis: bad argument");
     PM_CHECK_LD("pm_mdft_basis", ld_ok(M, N, E_ld));
     if (M == 0 || N == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(M, N, block);
-    if (dtype == PM_C64)
-        hipLaunchKernelGGL(mdft_basis_kernel<float>, grid, block, 0, PM_STREAM(stream), M, N, (const float*)f, (const float*)x, double(sign), (cx<float>*)E, E_ld);
-    else if (dtype == PM_C128)
-        hipLaunchKernelGGL(mdft_basis_kernel<double>, grid, block, 0, PM_STREAM(stream), M, N, (const double*)f, (const double*)x, double(sign), (cx<double>*)E, E_ld);
-    else
-        return fail(PM_ERR_ARG, "pm_mdft_basis: dtype must be PM_C64 or PM_C128");
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_mdft_basis", [&](auto real) {
+        using T = decltype(real);
+        return sweep(M, N, PM_STREAM(stream), MdftBasis<T>{(const T*)f, (const T*)x, double(sign), (cx<T>*)E, E_ld});
+    });
 }
 
 int pm_mdft_basis_grid(int32_t dtype, int64_t M, int64_t N, double f_step, double f_shift, double f_scale, double x_step,
@@ -948,32 +838,21 @@ int pm_mdft_basis_grid(int32_t dtype, int64_t M, int64_t N, double f_step, doubl
     if (!E || M < 0 || N < 0 || (sign != 1 && sign != -1)) return fail(PM_ERR_ARG, "pm_mdft_basis_grid: bad argument");
     PM_CHECK_LD("pm_mdft_basis_grid", ld_ok(M, N, E_ld));
     if (M == 0 || N == 0) return 0;
-    dim3 block;
-    dim3 grid = grid2d(M, N, block);
-    if (dtype == PM_C64)
-        hipLaunchKernelGGL(mdft_basis_grid_kernel<float>, grid, block, 0, PM_STREAM(stream), M, N, float(f_step), float(f_shift),
-                           float(f_scale), float(x_step), double(sign), (cx<float>*)E, E_ld);
-    else if (dtype == PM_C128)
-        hipLaunchKernelGGL(mdft_basis_grid_kernel<double>, grid, block, 0, PM_STREAM(stream), M, N, f_step, f_shift, f_scale, x_step,
-                           double(sign), (cx<double>*)E, E_ld);
-    else
-        return fail(PM_ERR_ARG, "pm_mdft_basis_grid: dtype must be PM_C64 or PM_C128");
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_mdft_basis_grid", [&](auto real) {
+        using T = decltype(real);
+        return sweep(M, N, PM_STREAM(stream), MdftBasisGrid<T>{M, N, T(f_step), T(f_shift), T(f_scale), T(x_step), double(sign), (cx<T>*)E, E_ld});
+    });
 }
 
 int pm_czt_vectors(int32_t dtype, int64_t N, int64_t M, int64_t K, double shift, double half, void* b, void* a, void* h, void* stream) {
     if (!b || !a || !h || N < 1 || M < 1 || K < N + M - 1) return fail(PM_ERR_ARG, "pm_czt_vectors: bad argument");
     const int64_t total = N + M + K;
     const dim3 grid((unsigned)((total + 255) / 256));
-    if (dtype == PM_C64)
-        hipLaunchKernelGGL(czt_vectors_kernel<float>, grid, dim3(256), 0, PM_STREAM(stream), N, M, K, shift, half, (cx<float>*)b, (cx<float>*)a,
-                           (cx<float>*)h);
-    else if (dtype == PM_C128)
-        hipLaunchKernelGGL(czt_vectors_kernel<double>, grid, dim3(256), 0, PM_STREAM(stream), N, M, K, shift, half, (cx<double>*)b,
-                           (cx<double>*)a, (cx<double>*)h);
-    else
-        return fail(PM_ERR_ARG, "pm_czt_vectors: dtype must be PM_C64 or PM_C128");
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_czt_vectors", [&](auto real) {
+        using T = decltype(real);
+        hipLaunchKernelGGL(czt_vectors_kernel<T>, grid, dim3(256), 0, PM_STREAM(stream), N, M, K, shift, half, (cx<T>*)b, (cx<T>*)a, (cx<T>*)h);
+        return int(hipGetLastError());
+    });
 }
 
 }  // extern "C"

@@ -16,7 +16,7 @@
 // every graph replay gives the same bits.
 #include "zernike_walk.h"
 
-#define PM_STREAM(s) reinterpret_cast<hipStream_t>(s)
+#include "pm_entry.h"
 
 namespace pm {
 namespace {

@@ -16,7 +16,7 @@
 // prysm_amd/segmented.py and checked by pm_segment_plan_check before it is uploaded.
 #include "zernike_walk.h"
 
-#define PM_STREAM(s) reinterpret_cast<hipStream_t>(s)
+#include "pm_entry.h"
 
 namespace pm {
 namespace {

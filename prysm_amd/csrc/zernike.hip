@@ -16,7 +16,7 @@
 // launch sums the partials of each output in a fixed order.  No atomics, so every run and every graph replay gives the same bits.
 #include "zernike_walk.h"
 
-#define PM_STREAM(s) reinterpret_cast<hipStream_t>(s)
+#include "pm_entry.h"
 
 namespace pm {
 namespace {

@@ -87,7 +87,7 @@ C_OUTER = 4         # one cmul (3)
 
 
 def c_sum_modes(nmodes):
-    return nmodes + 2   # sum_modes_kernel: one multiply-add per mode (nmodes), the accumulated start value and the final store (2)
+    return nmodes + 2   # SumModes: one multiply-add per mode (nmodes), the accumulated start value and the final store (2)
 
 
 @pytest.mark.parametrize('cdtype', CDTYPES)
