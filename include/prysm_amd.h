@@ -38,7 +38,7 @@ extern "C" {
 #define PM_VERSION 107 /* 0.1.0 */
 
 /* dtype codes */
-enum { PM_C64 = 0, PM_C128 = 1, PM_F32 = 2, PM_F64 = 3, PM_BOOL = 4 };
+enum { PM_C64 = 0, PM_C128 = 1, PM_F32 = 2, PM_F64 = 3, PM_BOOL = 4, PM_U8 = 5, PM_U16 = 6, PM_U32 = 7 };
 
 /* error codes (negative) */
 enum {
@@ -488,6 +488,53 @@ int pm_detector_expose(int32_t dtype, int64_t batch, int64_t ny, int64_t nx, con
 /* The four Philox words of draw block `block` of the pixels pixel0 .. pixel0 + npix - 1 at global frame index `frame`, to out (npix x 4
  * uint32): what the tests pin the kernels' generator with. */
 int pm_detector_words(int64_t seed, int64_t pixel0, int64_t npix, int64_t frame, int32_t block, void* out, void* stream);
+
+/* Bayer mosaics (csrc/bayer.hip): prysm/bayer.py.  The colour of a pixel is the parity of (row, col): PM_CFA_RGGB has R at (even, even),
+ * G1 at (even, odd), G2 at (odd, even), B at (odd, odd); PM_CFA_BGGR swaps R and B.  Stacks are batch x m x n with a row stride and a
+ * batch stride in elements; REAL data, PM_F32 or PM_F64.  prysm_amd/bayer_plan.py is the same arithmetic in numpy. */
+enum { PM_CFA_RGGB = 0, PM_CFA_BGGR = 1 };
+enum { PM_BAYER_COMPOSITE = 0, PM_BAYER_RECOMPOSITE = 1 };
+enum { PM_BAYER_MOSAIC = 0, PM_BAYER_RGB = 1 };
+
+/* demosaic_malvar (bayer.py:378-447, weights 344-375 divided by 8) as ONE kernel: in (batch x m x n; in_dtype PM_F32 / PM_F64 equal to
+ * out_dtype, or PM_U8 / PM_U16 / PM_U32 read as stored and converted in registers) to out, contiguous: batch x m x n x 3 interleaved
+ * R, G, B, or with planar != 0 batch x 3 x m x n.  Native sites are copies; every other value is one running sum over the taps of its
+ * filter in row-major order of the 5 x 5 footprint.  Boundary: scipy's mode='reflect' (index i of an axis of length n reads
+ * j = i mod 2n; j >= n ? 2n - 1 - j : j).  Any m, n >= 1. */
+int pm_bayer_demosaic(int32_t in_dtype, int32_t out_dtype, int32_t cfa, int32_t planar, int64_t batch, int64_t m, int64_t n, const void* in,
+                      int64_t in_ld, int64_t in_bstride, void* out, void* stream);
+
+/* composite_bayer (bayer.py:130-171; PM_BAYER_COMPOSITE: out[r][c] = plane(parity)[r][c], planes of m x n) and recomposite_bayer
+ * (bayer.py:213-257; PM_BAYER_RECOMPOSITE: out[2i + py][2j + px] = plane(parity)[i][j], planes of m/2 x n/2, m and n even).  out is
+ * batch x m x n.  Each plane has its own row, element and batch stride (in elements), so the stride-2 views of decomposite_bayer
+ * (bayer.py:174-210) go straight back in. */
+int pm_bayer_weave(int32_t dtype, int32_t mode, int32_t cfa, int64_t batch, int64_t m, int64_t n, const void* r, int64_t r_rs, int64_t r_es,
+                   int64_t r_bs, const void* g1, int64_t g1_rs, int64_t g1_es, int64_t g1_bs, const void* g2, int64_t g2_rs, int64_t g2_es,
+                   int64_t g2_bs, const void* b, int64_t b_rs, int64_t b_es, int64_t b_bs, void* out, int64_t out_ld, int64_t out_bstride,
+                   void* stream);
+
+/* demosaic_deinterlace (bayer.py:260-282): in (batch x m x n, m and n even) to out (batch x m/2 x n/2 x 3, contiguous) as r, (g1 + g2) / 2, b. */
+int pm_bayer_deinterlace(int32_t dtype, int32_t cfa, int64_t batch, int64_t m, int64_t n, const void* in, int64_t in_ld, int64_t in_bstride,
+                         void* out, void* stream);
+
+/* The last lines of assemble_superresolved (bayer.py:331-336): out (batch x m x n x 3, contiguous) = r, (g2 + g1) / 2, b from four planes
+ * of m x n with their own row, element and batch strides (the real part of a complex plane is a plane of element stride 2). */
+int pm_bayer_assemble(int32_t dtype, int64_t batch, int64_t m, int64_t n, const void* r, int64_t r_rs, int64_t r_es, int64_t r_bs, const void* g1,
+                      int64_t g1_rs, int64_t g1_es, int64_t g1_bs, const void* g2, int64_t g2_rs, int64_t g2_es, int64_t g2_bs, const void* b,
+                      int64_t b_rs, int64_t b_es, int64_t b_bs, void* out, void* stream);
+
+/* White balance without a host round trip (wb_prescale bayer.py:13-75, wb_postscale bayer.py:78-127).
+ * pm_bayer_class_max: the maxima of the classes of `in` to `maxima`, a DEVICE array of four doubles: PM_BAYER_MOSAIC the parity classes
+ * 2 (row & 1) + (col & 1) of batch x m x n; PM_BAYER_RGB the channels of batch x m x n x 3 (row stride >= 3 n; maxima[3] = -inf).  Two
+ * launches, comparisons only, deterministic; NaN propagates like numpy's max.  workspace: pm_bayer_class_max_workspace() DEVICE bytes.
+ * pm_bayer_scale: data *= the gain of its class, in place.  gains / saturation are HOST arrays in the reference's order (r, g1, g2, b
+ * for a mosaic, r, g, b for RGB).  With safe != 0 the kernel first divides the gains by `ratio`, computed in dtype from `maxima`:
+ * ratio = 1, then per class in that order rat = max * gain / sat, taken when rat > 1 and rat > ratio. */
+size_t pm_bayer_class_max_workspace(void);
+int pm_bayer_class_max(int32_t dtype, int32_t classes, int64_t batch, int64_t m, int64_t n, const void* in, int64_t in_ld, int64_t in_bstride,
+                       void* maxima, void* workspace, size_t workspace_bytes, void* stream);
+int pm_bayer_scale(int32_t dtype, int32_t classes, int32_t cfa, int64_t batch, int64_t m, int64_t n, void* data, int64_t ld, int64_t bstride,
+                   const double* gains, int32_t safe, const double* saturation, const void* maxima, void* stream);
 
 /* Segmented apertures (csrc/segmented.hip): CompositeHexagonalAperture.compose_opd (prysm/segmented.py:178-285) and its adjoint.
  * The grid is rows x cols REAL points (dtype PM_F32 / PM_F64, computed in that precision); x, y are the aperture's DEVICE coordinate

@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PRYSM_AMD_LIB') or os.path.join(_HERE, 'libprysm_amd.so')
 
 PM_C64, PM_C128, PM_F32, PM_F64, PM_BOOL = 0, 1, 2, 3, 4
+PM_U8, PM_U16, PM_U32 = 5, 6, 7
 PM_EPI_NONE, PM_EPI_ABS2, PM_EPI_ABS2_ACCUM, PM_EPI_ABS, PM_EPI_ARG = 0, 1, 2, 3, 4
 PM_MUL_NONE, PM_MUL_FULL, PM_MUL_SEPARABLE = 0, 1, 2
 PM_FLAG_PASS1_ONLY, PM_FLAG_PASS2_ONLY, PM_FLAG_REAL_INPUT, PM_FLAG_SYNTH_INPUT, PM_FLAG_NORM_DC, PM_FLAG_SYNTH_PACKED = 1, 2, 4, 8, 16, 32
@@ -29,6 +30,9 @@ PM_SEGMENT_ZERNIKE, PM_SEGMENT_STORED = 0, 1
 PM_COORDS_GRID, PM_COORDS_SEPARABLE, PM_COORDS_POINTWISE = 0, 1, 2
 PM_SDF_MASK, PM_SDF_DISTANCE, PM_SDF_COVERAGE = 0, 1, 2
 PM_BIN_AVG, PM_BIN_SUM = 0, 1
+PM_CFA_RGGB, PM_CFA_BGGR = 0, 1
+PM_BAYER_COMPOSITE, PM_BAYER_RECOMPOSITE = 0, 1
+PM_BAYER_MOSAIC, PM_BAYER_RGB = 0, 1
 
 c_i32, c_i64, c_f64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
 
@@ -121,6 +125,14 @@ SIGNATURES = {
     'pm_detector_expose': (c_i32, [c_i32, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_i32,
                                    c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
     'pm_detector_words': (c_i32, [c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp]),
+    'pm_bayer_demosaic': (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    'pm_bayer_weave': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_i64] + [c_vp, c_i64, c_i64, c_i64] * 4 + [c_vp, c_i64, c_i64, c_vp]),
+    'pm_bayer_deinterlace': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    'pm_bayer_assemble': (c_i32, [c_i32, c_i64, c_i64, c_i64] + [c_vp, c_i64, c_i64, c_i64] * 4 + [c_vp, c_vp]),
+    'pm_bayer_class_max_workspace': (c_sz, []),
+    'pm_bayer_class_max': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    'pm_bayer_scale': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, ctypes.POINTER(c_f64), c_i32, ctypes.POINTER(c_f64),
+                               c_vp, c_vp]),
     'pm_segment_plan_check': (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64]),
     'pm_segment_compose': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                    c_vp, c_i32, c_vp, c_vp]),
