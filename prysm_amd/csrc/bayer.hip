@@ -17,8 +17,8 @@
 //    Sum order of every filter: the taps in row-major order of the 5 x 5 footprint (north-2; north-west, north, north-east; west-2,
 //    west, centre, east, east-2; south-west, south, south-east; south-2), zero weights skipped, one running sum that starts at 0, each
 //    product rounded by itself (power-of-two weights are exact).  Boundary: scipy's mode='reflect' (the edge sample repeated).
-//  - pm_bayer_weave / pm_bayer_deinterlace / pm_bayer_assemble / pm_bayer_scale: row sweeps in the shape of pointwise.hip (64 adjacent
-//    columns per wave, 64 x 4 threads, threads striding down the rows), grid.z the member of a stack.
+//  - pm_bayer_weave / pm_bayer_deinterlace / pm_bayer_assemble / pm_bayer_scale: row sweeps (pm_sweep.h: 64 adjacent columns per wave,
+//    64 x 4 threads, threads striding down the rows) in its stacked form, grid.z the member of a stack.
 //  - pm_bayer_class_max: the maxima of the parity classes of a mosaic or of the channels of an RGB image, two launches (partials per
 //    workgroup, then one workgroup), comparisons only: no atomics, deterministic, NaN propagates as numpy's max does.
 //
@@ -27,9 +27,8 @@
 #include <algorithm>
 #include <cmath>
 
-#include "pm_internal.h"
-
 #include "pm_entry.h"
+#include "pm_sweep.h"
 
 namespace pm {
 namespace {
@@ -155,28 +154,6 @@ __global__ __launch_bounds__(kDemThreads) void demosaic_kernel(int64_t m, int64_
         }
     }
 }
-
-// ---------------------------------------------------------------- the row sweep of pointwise.hip with the member of a stack in grid.z
-template <typename F>
-__global__ void sweep_kernel(int64_t rows, int64_t cols, const F f) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    const int64_t b = blockIdx.z;
-    const auto col = f.column(c);
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y) f.point(b, r, c, col);
-}
-
-template <typename F>
-int sweep(int64_t batch, int64_t rows, int64_t cols, hipStream_t st, const F& f) {
-    const dim3 block(64, 4);
-    const int64_t gx = (cols + block.x - 1) / block.x;
-    int64_t gy = (rows + block.y - 1) / block.y;
-    if (gy > 65535) gy = 65535;
-    hipLaunchKernelGGL(sweep_kernel<F>, dim3((unsigned)gx, (unsigned)gy, (unsigned)batch), block, 0, st, rows, cols, f);
-    return int(hipGetLastError());
-}
-
-struct NoColumn {};
 
 // a plane of a stack: element (b, r, c) at p[b * bs + r * rs + c * es]
 template <typename T>
@@ -330,14 +307,12 @@ struct Scale {
     }
 };
 
-bool real_dtype(int32_t dtype) { return dtype == PM_F32 || dtype == PM_F64; }
-
 // what every entry point checks of (batch, m, n) read through a row stride and a batch stride of `row` elements per row
 int check_stack(const char* who, int64_t batch, int64_t m, int64_t n, int64_t row, int64_t ld, int64_t bstride) {
     if (batch < 1 || m < 1 || n < 1) return fail(PM_ERR_ARG, "%s: batch, m and n must be at least 1, got %lld, %lld, %lld", who, (long long)batch, (long long)m, (long long)n);
     if (m > INT32_MAX || n > INT32_MAX / 4 || batch > 65535) return fail(PM_ERR_ARG, "%s: %lld x %lld x %lld is too large", who, (long long)batch, (long long)m, (long long)n);
     if (ld < row) return fail(PM_ERR_ARG, "%s: the row stride %lld is smaller than the row of %lld", who, (long long)ld, (long long)row);
-    if (batch > 1 && bstride < m * ld) return fail(PM_ERR_ARG, "%s: bstride: the members of a stack would overlap", who);
+    if (!stack_ok(batch, m, ld, bstride)) return fail(PM_ERR_ARG, "%s: bstride: the members of a stack would overlap", who);
     return 0;
 }
 int check_cfa(const char* who, int32_t cfa) {
@@ -387,9 +362,9 @@ int pm_bayer_demosaic(int32_t in_dtype, int32_t out_dtype, int32_t cfa, int32_t 
     if (int rc = check_stack(who, batch, m, n, n, in_ld, in_bstride)) return rc;
     if ((m + kTileH - 1) / kTileH > 65535) return fail(PM_ERR_ARG, "%s: %lld rows are too many", who, (long long)m);
     if (!in || !out) return fail(PM_ERR_ARG, "%s: null pointer", who);
-    hipStream_t st = PM_STREAM(stream);
-    if (out_dtype == PM_F32) return demosaic_by_input<float>(in_dtype, planar != 0, batch, m, n, cfa, in, in_ld, in_bstride, out, st);
-    return demosaic_by_input<double>(in_dtype, planar != 0, batch, m, n, cfa, in, in_ld, in_bstride, out, st);
+    return by_rdtype(out_dtype, who, [&](auto real) {
+        return demosaic_by_input<decltype(real)>(in_dtype, planar != 0, batch, m, n, cfa, in, in_ld, in_bstride, out, PM_STREAM(stream));
+    });
 }
 
 int pm_bayer_weave(int32_t dtype, int32_t mode, int32_t cfa, int64_t batch, int64_t m, int64_t n, const void* r, int64_t r_rs, int64_t r_es,
@@ -407,15 +382,14 @@ int pm_bayer_weave(int32_t dtype, int32_t mode, int32_t cfa, int64_t batch, int6
     const void* last = cfa == PM_CFA_RGGB ? b : r;
     const int64_t f_rs = cfa == PM_CFA_RGGB ? r_rs : b_rs, f_es = cfa == PM_CFA_RGGB ? r_es : b_es, f_bs = cfa == PM_CFA_RGGB ? r_bs : b_bs;
     const int64_t l_rs = cfa == PM_CFA_RGGB ? b_rs : r_rs, l_es = cfa == PM_CFA_RGGB ? b_es : r_es, l_bs = cfa == PM_CFA_RGGB ? b_bs : r_bs;
-    auto go = [&](auto real) {
+    return by_rdtype(dtype, who, [&](auto real) {
         using T = decltype(real);
         Weave<T> w;
         w.pl[0] = plane_of<T>(first, f_rs, f_es, f_bs), w.pl[1] = plane_of<T>(g1, g1_rs, g1_es, g1_bs);
         w.pl[2] = plane_of<T>(g2, g2_rs, g2_es, g2_bs), w.pl[3] = plane_of<T>(last, l_rs, l_es, l_bs);
         w.half = mode == PM_BAYER_RECOMPOSITE, w.o = static_cast<T*>(out), w.ldo = out_ld, w.bso = out_bstride;
         return sweep(batch, m, n, PM_STREAM(stream), w);
-    };
-    return dtype == PM_F32 ? go(float{}) : go(double{});
+    });
 }
 
 int pm_bayer_deinterlace(int32_t dtype, int32_t cfa, int64_t batch, int64_t m, int64_t n, const void* in, int64_t in_ld, int64_t in_bstride,
@@ -426,11 +400,10 @@ int pm_bayer_deinterlace(int32_t dtype, int32_t cfa, int64_t batch, int64_t m, i
     if (int rc = check_stack(who, batch, m, n, n, in_ld, in_bstride)) return rc;
     if ((m | n) & 1) return fail(PM_ERR_ARG, "%s: m and n must be even, got %lld x %lld", who, (long long)m, (long long)n);
     if (!in || !out) return fail(PM_ERR_ARG, "%s: null pointer", who);
-    auto go = [&](auto real) {
+    return by_rdtype(dtype, who, [&](auto real) {
         using T = decltype(real);
         return sweep(batch, m / 2, n / 2, PM_STREAM(stream), Deinterlace<T>{static_cast<const T*>(in), in_ld, in_bstride, cfa, m / 2, n / 2, static_cast<T*>(out)});
-    };
-    return dtype == PM_F32 ? go(float{}) : go(double{});
+    });
 }
 
 int pm_bayer_assemble(int32_t dtype, int64_t batch, int64_t m, int64_t n, const void* r, int64_t r_rs, int64_t r_es, int64_t r_bs, const void* g1,
@@ -440,13 +413,12 @@ int pm_bayer_assemble(int32_t dtype, int64_t batch, int64_t m, int64_t n, const 
     if (!real_dtype(dtype)) return fail(PM_ERR_ARG, "%s: dtype must be PM_F32 or PM_F64", who);
     if (int rc = check_stack(who, batch, m, n, n, n, m * n)) return rc;
     if (!r || !g1 || !g2 || !b || !out) return fail(PM_ERR_ARG, "%s: null pointer", who);
-    auto go = [&](auto real) {
+    return by_rdtype(dtype, who, [&](auto real) {
         using T = decltype(real);
         return sweep(batch, m, n, PM_STREAM(stream),
                      Assemble<T>{plane_of<T>(r, r_rs, r_es, r_bs), plane_of<T>(g1, g1_rs, g1_es, g1_bs), plane_of<T>(g2, g2_rs, g2_es, g2_bs),
                                  plane_of<T>(b, b_rs, b_es, b_bs), m, n, static_cast<T*>(out)});
-    };
-    return dtype == PM_F32 ? go(float{}) : go(double{});
+    });
 }
 
 size_t pm_bayer_class_max_workspace(void) { return size_t(kMaxPartials) * 4 * sizeof(double); }
@@ -468,11 +440,12 @@ int pm_bayer_class_max(int32_t dtype, int32_t classes, int64_t batch, int64_t m,
     hipStream_t st = PM_STREAM(stream);
     const dim3 grid{unsigned(gx), unsigned(gy)}, block(64, 4);
     double* part = static_cast<double*>(workspace);
-    if (dtype == PM_F32)
-        hipLaunchKernelGGL(class_max_kernel<float>, grid, block, 0, st, nclass, batch, m, cols, static_cast<const float*>(in), in_ld, in_bstride, part);
-    else
-        hipLaunchKernelGGL(class_max_kernel<double>, grid, block, 0, st, nclass, batch, m, cols, static_cast<const double*>(in), in_ld, in_bstride, part);
-    if (int rc = int(hipGetLastError())) return rc;
+    const int rc = by_rdtype(dtype, who, [&](auto real) {
+        using T = decltype(real);
+        hipLaunchKernelGGL(class_max_kernel<T>, grid, block, 0, st, nclass, batch, m, cols, static_cast<const T*>(in), in_ld, in_bstride, part);
+        return int(hipGetLastError());
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(class_max_final_kernel, dim3{1}, dim3{256}, 0, st, gx * gy, part, static_cast<double*>(maxima));
     return int(hipGetLastError());
 }
@@ -496,11 +469,10 @@ int pm_bayer_scale(int32_t dtype, int32_t classes, int32_t cfa, int64_t batch, i
         if (safe && k < nclass && !(g.sat[k] > 0.0)) return fail(PM_ERR_ARG, "%s: saturation must be positive", who);
     }
     if (nclass == 4 && cfa == PM_CFA_BGGR) g.cls[0] = 3, g.cls[3] = 0;      // r sits at (odd, odd), b at (even, even)
-    auto go = [&](auto real) {
+    return by_rdtype(dtype, who, [&](auto real) {
         using T = decltype(real);
         return sweep(batch, m, cols, PM_STREAM(stream), Scale<T>{nclass, safe != 0, g, static_cast<const double*>(maxima), static_cast<T*>(data), ld, bstride});
-    };
-    return dtype == PM_F32 ? go(float{}) : go(double{});
+    });
 }
 
 }  // extern "C"

@@ -19,8 +19,6 @@
 // (csrc/Makefile) so that every product and sum is rounded by itself, as numpy does; all thresholds and sums are fp64.
 #include <cmath>
 
-#include "pm_internal.h"
-
 #include "pm_entry.h"
 
 namespace pm {
@@ -256,8 +254,6 @@ __global__ __launch_bounds__(kThreads) void tile_kernel(int64_t oy, int64_t ox, 
     out[int64_t(blockIdx.y) * out_bstride + r * out_ld + c] = v;
 }
 
-bool real_dtype(int32_t dtype) { return dtype == PM_F32 || dtype == PM_F64; }
-bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 int64_t blocks_of(int64_t n) { return (n + kThreads - 1) / kThreads; }
 bool width_ok(int32_t out_bytes) { return out_bytes == 1 || out_bytes == 2 || out_bytes == 4 || out_bytes == 8; }
 
@@ -268,7 +264,7 @@ int check_tail(const char* who, int32_t dtype, int64_t batch, int64_t ny, int64_
     if (bits < 1 || bits > 32) return fail(PM_ERR_ARG, "%s: bits must be in 1 .. 32, got %d", who, int(bits));
     if (batch < 0 || ny < 0 || nx < 0 || !in || !out) return fail(PM_ERR_ARG, "%s: bad argument (null pointer or negative size)", who);
     if (ld < nx) return fail(PM_ERR_ARG, "%s: ld %lld is smaller than the row of %lld", who, (long long)ld, (long long)nx);
-    if (batch > 1 && bstride < ny * ld) return fail(PM_ERR_ARG, "%s: bstride: the members of a stack would overlap", who);
+    if (!stack_ok(batch, ny, ld, bstride)) return fail(PM_ERR_ARG, "%s: bstride: the members of a stack would overlap", who);
     if (!(conversion_gain != 0.0) || !std::isfinite(conversion_gain)) return fail(PM_ERR_ARG, "%s: conversion_gain must be finite and not 0", who);
     if (!width_ok(out_bytes)) return fail(PM_ERR_ARG, "%s: out_bytes must be 1, 2, 4 or 8", who);
     if (lut && lut_len < (int64_t(1) << bits))
@@ -280,52 +276,10 @@ int check_tail(const char* who, int32_t dtype, int64_t batch, int64_t ny, int64_
     return 0;
 }
 
-template <typename T>
-void launch_expose(int32_t out_bytes, const ExposeArgs& a, dim3 grid, hipStream_t st) {
-    const dim3 block{kThreads};
-    switch (out_bytes) {
-    case 1: hipLaunchKernelGGL((expose_kernel<T, uint8_t>), grid, block, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((expose_kernel<T, uint16_t>), grid, block, 0, st, a); break;
-    case 4: hipLaunchKernelGGL((expose_kernel<T, uint32_t>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((expose_kernel<T, uint64_t>), grid, block, 0, st, a); break;
-    }
-}
-
-template <typename T>
-void launch_digitize(int32_t out_bytes, int64_t n, int64_t plane, int64_t nx, const void* in, int64_t ld, int64_t bstride, const Tail& t,
-                     void* out, hipStream_t st) {
-    const dim3 grid{unsigned(blocks_of(n))}, block{kThreads};
-    const T* src = static_cast<const T*>(in);
-    switch (out_bytes) {
-    case 1: hipLaunchKernelGGL((digitize_kernel<T, uint8_t>), grid, block, 0, st, n, plane, nx, src, ld, bstride, t, (uint8_t*)out); break;
-    case 2: hipLaunchKernelGGL((digitize_kernel<T, uint16_t>), grid, block, 0, st, n, plane, nx, src, ld, bstride, t, (uint16_t*)out); break;
-    case 4: hipLaunchKernelGGL((digitize_kernel<T, uint32_t>), grid, block, 0, st, n, plane, nx, src, ld, bstride, t, (uint32_t*)out); break;
-    default: hipLaunchKernelGGL((digitize_kernel<T, uint64_t>), grid, block, 0, st, n, plane, nx, src, ld, bstride, t, (uint64_t*)out); break;
-    }
-}
-
 Tail make_tail(double bias, double fwc, double conversion_gain, int32_t bits, const void* lut) {
     Tail t;
     t.bias = bias, t.fwc = fwc, t.inv_gain = 1 / conversion_gain, t.cap = double((int64_t(1) << bits) - 1), t.lut = lut;
     return t;
-}
-
-template <typename T>
-void launch_bindown(int64_t batch, int64_t my, int64_t nx, int64_t fy, int64_t fx, int avg, const void* in, int64_t in_ld, int64_t in_bstride,
-                    void* out, int64_t out_ld, int64_t out_bstride, hipStream_t st) {
-    const dim3 grid{unsigned(blocks_of(my * nx)), unsigned(batch)}, block{kThreads};
-    const T* src = static_cast<const T*>(in);
-    T* dst = static_cast<T*>(out);
-    const size_t es = sizeof(T);
-    // pieces of C elements: the factor is a multiple of C and every bin row starts on a multiple of C * es bytes
-    auto fits = [&](int C) { return fx % C == 0 && aligned(in, C * es) && (in_ld * es) % (C * es) == 0 && (in_bstride * es) % (C * es) == 0; };
-    const int C = (16 / es >= 4 && fits(4)) ? 4 : fits(2) ? 2 : 1;
-    if (C == 4)
-        hipLaunchKernelGGL((bindown_kernel<T, 4>), grid, block, 0, st, my, nx, fy, fx, avg, src, in_ld, in_bstride, dst, out_ld, out_bstride);
-    else if (C == 2)
-        hipLaunchKernelGGL((bindown_kernel<T, 2>), grid, block, 0, st, my, nx, fy, fx, avg, src, in_ld, in_bstride, dst, out_ld, out_bstride);
-    else
-        hipLaunchKernelGGL((bindown_kernel<T, 1>), grid, block, 0, st, my, nx, fy, fx, avg, src, in_ld, in_bstride, dst, out_ld, out_bstride);
 }
 
 // shared by pm_bindown and pm_tile: (my, nx) is the SMALL array, the large one is (my fy, nx fx)
@@ -339,7 +293,7 @@ int check_bin(const char* who, int32_t dtype, int64_t batch, int64_t my, int64_t
         return fail(PM_ERR_ARG, "%s: %lld x %lld by %lld x %lld (stack of %lld) is too large", who, (long long)my, (long long)nx, (long long)fy,
                     (long long)fx, (long long)batch);
     if (big_ld < nx * fx || small_ld < nx) return fail(PM_ERR_ARG, "%s: a leading dimension is smaller than its row", who);
-    if (batch > 1 && (big_bstride < my * fy * big_ld || small_bstride < my * small_ld))
+    if (!stack_ok(batch, my * fy, big_ld, big_bstride) || !stack_ok(batch, my, small_ld, small_bstride))
         return fail(PM_ERR_ARG, "%s: bstride: the members of a stack would overlap", who);
     return 0;
 }
@@ -356,12 +310,24 @@ int pm_bindown(int32_t dtype, int64_t batch, int64_t my, int64_t nx, int64_t fy,
     if (mode != PM_BIN_AVG && mode != PM_BIN_SUM) return fail(PM_ERR_ARG, "pm_bindown: mode must be PM_BIN_AVG or PM_BIN_SUM");
     if (int rc = check_bin("pm_bindown", dtype, batch, my, nx, fy, fx, in, in_ld, in_bstride, out_ld, out_bstride, out)) return rc;
     if (batch == 0 || my == 0 || nx == 0) return 0;
-    hipStream_t st = PM_STREAM(stream);
-    if (dtype == PM_F32)
-        launch_bindown<float>(batch, my, nx, fy, fx, mode == PM_BIN_AVG, in, in_ld, in_bstride, out, out_ld, out_bstride, st);
-    else
-        launch_bindown<double>(batch, my, nx, fy, fx, mode == PM_BIN_AVG, in, in_ld, in_bstride, out, out_ld, out_bstride, st);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_bindown", [&](auto real) {
+        using T = decltype(real);
+        const size_t es = sizeof(T);
+        // pieces of C elements: the factor is a multiple of C and every bin row starts on a multiple of C * es bytes
+        auto fits = [&](int C) { return fx % C == 0 && aligned(in, C * es) && (in_ld * es) % (C * es) == 0 && (in_bstride * es) % (C * es) == 0; };
+        auto launch = [&](auto pieces) {
+            hipLaunchKernelGGL((bindown_kernel<T, decltype(pieces)::value>), dim3(unsigned(blocks_of(my * nx)), unsigned(batch)), dim3(kThreads), 0,
+                               PM_STREAM(stream), my, nx, fy, fx, mode == PM_BIN_AVG, static_cast<const T*>(in), in_ld, in_bstride,
+                               static_cast<T*>(out), out_ld, out_bstride);
+        };
+        if (16 / es >= 4 && fits(4))
+            launch(std::integral_constant<int, 4>{});
+        else if (fits(2))
+            launch(std::integral_constant<int, 2>{});
+        else
+            launch(std::integral_constant<int, 1>{});
+        return int(hipGetLastError());
+    });
 }
 
 int pm_tile(int32_t dtype, int64_t batch, int64_t my, int64_t nx, int64_t fy, int64_t fx, double scale, const void* in, int64_t in_ld,
@@ -369,15 +335,13 @@ int pm_tile(int32_t dtype, int64_t batch, int64_t my, int64_t nx, int64_t fy, in
     if (!std::isfinite(scale)) return fail(PM_ERR_ARG, "pm_tile: scale must be finite");
     if (int rc = check_bin("pm_tile", dtype, batch, my, nx, fy, fx, in, out_ld, out_bstride, in_ld, in_bstride, out)) return rc;
     if (batch == 0 || my == 0 || nx == 0) return 0;
-    hipStream_t st = PM_STREAM(stream);
-    const dim3 grid{unsigned(blocks_of(my * fy * nx * fx)), unsigned(batch)}, block{kThreads};
-    if (dtype == PM_F32)
-        hipLaunchKernelGGL(tile_kernel<float>, grid, block, 0, st, my * fy, nx * fx, fy, fx, float(scale), scale != 1.0, (const float*)in, in_ld,
-                           in_bstride, (float*)out, out_ld, out_bstride);
-    else
-        hipLaunchKernelGGL(tile_kernel<double>, grid, block, 0, st, my * fy, nx * fx, fy, fx, scale, scale != 1.0, (const double*)in, in_ld,
-                           in_bstride, (double*)out, out_ld, out_bstride);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_tile", [&](auto real) {
+        using T = decltype(real);
+        hipLaunchKernelGGL(tile_kernel<T>, dim3(unsigned(blocks_of(my * fy * nx * fx)), unsigned(batch)), dim3(kThreads), 0, PM_STREAM(stream),
+                           my * fy, nx * fx, fy, fx, T(scale), scale != 1.0, static_cast<const T*>(in), in_ld, in_bstride, static_cast<T*>(out),
+                           out_ld, out_bstride);
+        return int(hipGetLastError());
+    });
 }
 
 int pm_detector_digitize(int32_t dtype, int64_t batch, int64_t ny, int64_t nx, const void* electrons, int64_t ld, int64_t bstride, double bias,
@@ -388,12 +352,15 @@ int pm_detector_digitize(int32_t dtype, int64_t batch, int64_t ny, int64_t nx, c
     const int64_t n = batch * ny * nx;
     if (n == 0) return 0;
     const Tail t = make_tail(bias, fwc, conversion_gain, bits, lut);
-    hipStream_t st = PM_STREAM(stream);
-    if (dtype == PM_F32)
-        launch_digitize<float>(out_bytes, n, ny * nx, nx, electrons, ld, bstride, t, out, st);
-    else
-        launch_digitize<double>(out_bytes, n, ny * nx, nx, electrons, ld, bstride, t, out, st);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_detector_digitize", [&](auto real) {
+        return by_uint_bytes(out_bytes, "pm_detector_digitize", [&](auto sample) {
+            using T = decltype(real);
+            using O = decltype(sample);
+            hipLaunchKernelGGL((digitize_kernel<T, O>), dim3(unsigned(blocks_of(n))), dim3(kThreads), 0, PM_STREAM(stream), n, ny * nx, nx,
+                               static_cast<const T*>(electrons), ld, bstride, t, static_cast<O*>(out));
+            return int(hipGetLastError());
+        });
+    });
 }
 
 int pm_detector_expose(int32_t dtype, int64_t batch, int64_t ny, int64_t nx, const void* img, int64_t ld, int64_t bstride, const void* prnu,
@@ -421,11 +388,13 @@ int pm_detector_expose(int32_t dtype, int64_t batch, int64_t ny, int64_t nx, con
     a.fchunk = (frames + chunks - 1) / chunks;
     const dim3 grid{unsigned(blocks), unsigned((frames + a.fchunk - 1) / a.fchunk)};
     hipStream_t st = PM_STREAM(stream);
-    if (dtype == PM_F32)
-        launch_expose<float>(out_bytes, a, grid, st);
-    else
-        launch_expose<double>(out_bytes, a, grid, st);
-    if (int rc = int(hipGetLastError())) return rc;
+    const int rc = by_rdtype(dtype, "pm_detector_expose", [&](auto real) {
+        return by_uint_bytes(out_bytes, "pm_detector_expose", [&](auto sample) {
+            hipLaunchKernelGGL((expose_kernel<decltype(real), decltype(sample)>), grid, dim3(kThreads), 0, st, a);
+            return int(hipGetLastError());
+        });
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(advance_kernel, dim3{1}, dim3{64}, 0, st, a.state, frames);
     return int(hipGetLastError());
 }

@@ -11,8 +11,6 @@
 // fp32: |z|^14 = 1e-8) and writes the coefficient image into the workspace; a second launch evaluates the 4 x 4 tap B-spline per
 // output pixel.  A coordinate outside [0, n - 1] on either axis gives exactly 0 (scipy's constant mode has no tolerance there);
 // inside, taps past an edge read the coefficients mirrored about it.  Coordinates are computed in fp64 in both precisions.
-#include "pm_internal.h"
-
 #include "pm_entry.h"
 
 namespace pm {
@@ -208,19 +206,16 @@ dim3 grid_of(int64_t cols, int64_t rows, int64_t batch, dim3 block) {
                 unsigned(batch < kMaxGridZ ? batch : kMaxGridZ));
 }
 
-template <typename T>
-void launch_warp(bool cx, int64_t batch, int rows, int cols, const void* in, int64_t in_ld, int64_t in_bstride, const Homography& H,
-                 double scale, int out_rows, int out_cols, int off_y, int off_x, void* out, int64_t out_ld, int64_t out_bstride, void* ws,
-                 hipStream_t st) {
-    const dim3 fblock(kFirThreads);
-    const dim3 fgrid = grid_of(cols, rows, batch, dim3(kFirTX, kFirTY));
-    if (cx)
-        hipLaunchKernelGGL((spline_fir_kernel<T, true>), fgrid, fblock, 0, st, batch, rows, cols, (const T*)in, in_ld, in_bstride, (T*)ws);
-    else
-        hipLaunchKernelGGL((spline_fir_kernel<T, false>), fgrid, fblock, 0, st, batch, rows, cols, (const T*)in, in_ld, in_bstride, (T*)ws);
-    const dim3 sblock(kLatticeBlockX, kLatticeBlockY);
-    hipLaunchKernelGGL(spline_sample_kernel<T>, grid_of(out_cols, out_rows, batch, sblock), sblock, 0, st, batch, rows, cols, (const T*)ws, H,
-                       scale, out_rows, out_cols, off_y, off_x, (T*)out, out_ld, out_bstride);
+// Calls f(real, cx) for a dtype that real_or_complex() has passed: real is a value of the dtype's real type, cx std::true_type for
+// the two complex dtypes (the kernels then read the real part of interleaved complex elements)
+template <typename F>
+int by_real_part(int32_t dtype, F&& f) {
+    switch (dtype) {
+        case PM_F32: return f(float{}, std::false_type{});
+        case PM_F64: return f(double{}, std::false_type{});
+        case PM_C64: return f(float{}, std::true_type{});
+        default: return f(double{}, std::true_type{});
+    }
 }
 
 }  // namespace
@@ -255,28 +250,21 @@ int pm_lattice(int32_t dtype, int32_t op, int64_t batch, int64_t rows, int64_t c
     if (batch == 0) return 0;
     hipStream_t st = PM_STREAM(stream);
     const dim3 block(kLatticeBlockX, kLatticeBlockY);
-    if (op == PM_LATTICE_SCATTER) {
-        const dim3 grid = grid_of(cols, rows, batch, block);
-        if (dtype == PM_F32)
-            hipLaunchKernelGGL(lattice_scatter_kernel<float>, grid, block, 0, st, batch, int(rows), int(cols), int(nact_y), int(nact_x), int(y0),
-                               int(x0), int(sy), int(sx), float(scale), (const float*)in, in_ld, in_bstride, (float*)out, out_ld, out_bstride);
-        else
-            hipLaunchKernelGGL(lattice_scatter_kernel<double>, grid, block, 0, st, batch, int(rows), int(cols), int(nact_y), int(nact_x), int(y0),
-                               int(x0), int(sy), int(sx), scale, (const double*)in, in_ld, in_bstride, (double*)out, out_ld, out_bstride);
+    if (op == PM_LATTICE_SCATTER)
+        return by_rdtype(dtype, "pm_lattice", [&](auto real) {
+            using T = decltype(real);
+            hipLaunchKernelGGL(lattice_scatter_kernel<T>, grid_of(cols, rows, batch, block), block, 0, st, batch, int(rows), int(cols), int(nact_y),
+                               int(nact_x), int(y0), int(x0), int(sy), int(sx), T(scale), static_cast<const T*>(in), in_ld, in_bstride,
+                               static_cast<T*>(out), out_ld, out_bstride);
+            return int(hipGetLastError());
+        });
+    return by_real_part(dtype, [&](auto real, auto cx) {
+        using T = decltype(real);
+        hipLaunchKernelGGL((lattice_gather_kernel<T, decltype(cx)::value>), grid_of(nact_x, nact_y, batch, block), block, 0, st, batch, int(nact_y),
+                           int(nact_x), int(y0), int(x0), int(sy), int(sx), T(scale), static_cast<const T*>(in), in_ld, in_bstride,
+                           static_cast<T*>(out), out_ld, out_bstride);
         return int(hipGetLastError());
-    }
-    const dim3 grid = grid_of(nact_x, nact_y, batch, block);
-#define PM_GATHER(T, CX)                                                                                                                    \
-    hipLaunchKernelGGL((lattice_gather_kernel<T, CX>), grid, block, 0, st, batch, int(nact_y), int(nact_x), int(y0), int(x0), int(sy), \
-                       int(sx), T(scale), (const T*)in, in_ld, in_bstride, (T*)out, out_ld, out_bstride)
-    switch (dtype) {
-        case PM_F32: PM_GATHER(float, false); break;
-        case PM_F64: PM_GATHER(double, false); break;
-        case PM_C64: PM_GATHER(float, true); break;
-        default: PM_GATHER(double, true); break;
-    }
-#undef PM_GATHER
-    return int(hipGetLastError());
+    });
 }
 
 size_t pm_warp_workspace(int32_t dtype, int64_t batch, int64_t rows, int64_t cols) {
@@ -302,15 +290,17 @@ int pm_warp(int32_t dtype, int32_t order, int64_t batch, int64_t rows, int64_t c
         return fail(PM_ERR_WORKSPACE, "pm_warp: workspace of %zu bytes is smaller than the %zu pm_warp_workspace asks for", workspace_bytes, need);
     Homography H;
     for (int k = 0; k < 9; ++k) H.m[k] = homography[k];
-    hipStream_t st = PM_STREAM(stream);
-    const bool cx = dtype == PM_C64 || dtype == PM_C128;
-    if (dtype == PM_F32 || dtype == PM_C64)
-        launch_warp<float>(cx, batch, int(rows), int(cols), in, in_ld, in_bstride, H, scale, int(out_rows), int(out_cols), int(off_y), int(off_x),
-                           out, out_ld, out_bstride, workspace, st);
-    else
-        launch_warp<double>(cx, batch, int(rows), int(cols), in, in_ld, in_bstride, H, scale, int(out_rows), int(out_cols), int(off_y),
-                            int(off_x), out, out_ld, out_bstride, workspace, st);
-    return int(hipGetLastError());
+    return by_real_part(dtype, [&](auto real, auto cx) {
+        using T = decltype(real);
+        hipStream_t st = PM_STREAM(stream);
+        T* coeff = static_cast<T*>(workspace);
+        hipLaunchKernelGGL((spline_fir_kernel<T, decltype(cx)::value>), grid_of(cols, rows, batch, dim3(kFirTX, kFirTY)), dim3(kFirThreads), 0, st,
+                           batch, int(rows), int(cols), static_cast<const T*>(in), in_ld, in_bstride, coeff);
+        const dim3 block(kLatticeBlockX, kLatticeBlockY);
+        hipLaunchKernelGGL(spline_sample_kernel<T>, grid_of(out_cols, out_rows, batch, block), block, 0, st, batch, int(rows), int(cols), coeff, H,
+                           scale, int(out_rows), int(out_cols), int(off_y), int(off_x), static_cast<T*>(out), out_ld, out_bstride);
+        return int(hipGetLastError());
+    });
 }
 
 }  // extern "C"

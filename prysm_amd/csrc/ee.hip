@@ -4,8 +4,6 @@
 // HBM bound on the MTF read (one pass serves up to 8 radii); the Bessel function is evaluated in fp64 for both precisions and the
 // sums are accumulated in fp64 in a fixed order (fixed grid, tree reduction, second kernel over the per-workgroup partials), so
 // results are reproducible run to run.
-#include "pm_internal.h"
-
 #include "pm_entry.h"
 
 namespace pm {
@@ -114,20 +112,20 @@ int pm_encircled_energy(int32_t dtype, int64_t rows, int64_t cols, const void* m
     int64_t nb = (rows * cols + kEeThreads - 1) / kEeThreads;
     if (nb > kEeBlocks) nb = kEeBlocks;
     const double cell = df * df;   // dnx * dny of the square frequency grid (otf.py:342)
-    for (int64_t r0 = 0; r0 < nradii; r0 += kEeMaxRadii) {   // 8 radii per pass over the MTF
-        const int nr = int(nradii - r0 < kEeMaxRadii ? nradii - r0 : kEeMaxRadii);
-        EeRadii rr;
-        for (int i = 0; i < kEeMaxRadii; ++i) {
-            rr.r[i] = i < nr ? radii_mm[r0 + i] : 0.0;
-            rr.w[i] = 0.0;
+    return by_cdtype(dtype, "pm_encircled_energy", [&](auto real) {
+        using T = decltype(real);
+        for (int64_t r0 = 0; r0 < nradii; r0 += kEeMaxRadii) {   // 8 radii per pass over the MTF
+            const int nr = int(nradii - r0 < kEeMaxRadii ? nradii - r0 : kEeMaxRadii);
+            EeRadii rr;
+            for (int i = 0; i < kEeMaxRadii; ++i) {
+                rr.r[i] = i < nr ? radii_mm[r0 + i] : 0.0;
+                rr.w[i] = 0.0;
+            }
+            hipLaunchKernelGGL(ee_reduce_kernel<T>, dim3(unsigned(nb)), dim3(kEeThreads), 0, st, rows, cols, static_cast<const T*>(mtf), mtf_ld, df, rr, nr, partial);
+            hipLaunchKernelGGL(ee_final_kernel, dim3(1), dim3(kEeThreads), 0, st, partial, int(nb), rr, nr, cell, out + r0);
         }
-        if (dtype == PM_C64)
-            hipLaunchKernelGGL(ee_reduce_kernel<float>, dim3(unsigned(nb)), dim3(kEeThreads), 0, st, rows, cols, (const float*)mtf, mtf_ld, df, rr, nr, partial);
-        else
-            hipLaunchKernelGGL(ee_reduce_kernel<double>, dim3(unsigned(nb)), dim3(kEeThreads), 0, st, rows, cols, (const double*)mtf, mtf_ld, df, rr, nr, partial);
-        hipLaunchKernelGGL(ee_final_kernel, dim3(1), dim3(kEeThreads), 0, st, partial, int(nb), rr, nr, cell, out + r0);
-    }
-    return int(hipGetLastError());
+        return int(hipGetLastError());
+    });
 }
 
 int pm_encircled_energy_adjoint(int32_t dtype, int64_t rows, int64_t cols, double df, int64_t nradii, const double* radii_mm,
@@ -139,23 +137,23 @@ int pm_encircled_energy_adjoint(int32_t dtype, int64_t rows, int64_t cols, doubl
     const int64_t total = rows * cols;
     const dim3 grid(unsigned((total + 255) / 256)), block(256);
     const double cell = df * df;
-    int acc = 0;
-    int64_t r0 = 0;
-    do {   // an empty radius list still writes zeros
-        const int nr = int(nradii - r0 < kEeMaxRadii ? nradii - r0 : kEeMaxRadii);
-        EeRadii rr;
-        for (int i = 0; i < kEeMaxRadii; ++i) {
-            rr.r[i] = i < nr ? radii_mm[r0 + i] : 0.0;
-            rr.w[i] = i < nr ? ee_bar[r0 + i] : 0.0;
-        }
-        if (dtype == PM_C64)
-            hipLaunchKernelGGL(ee_adjoint_kernel<float>, grid, block, 0, st, rows, cols, df, rr, nr, cell, acc, (float*)mtf_bar, mtf_bar_ld);
-        else
-            hipLaunchKernelGGL(ee_adjoint_kernel<double>, grid, block, 0, st, rows, cols, df, rr, nr, cell, acc, (double*)mtf_bar, mtf_bar_ld);
-        acc = 1;
-        r0 += kEeMaxRadii;
-    } while (r0 < nradii);
-    return int(hipGetLastError());
+    return by_cdtype(dtype, "pm_encircled_energy_adjoint", [&](auto real) {
+        using T = decltype(real);
+        int acc = 0;
+        int64_t r0 = 0;
+        do {   // an empty radius list still writes zeros
+            const int nr = int(nradii - r0 < kEeMaxRadii ? nradii - r0 : kEeMaxRadii);
+            EeRadii rr;
+            for (int i = 0; i < kEeMaxRadii; ++i) {
+                rr.r[i] = i < nr ? radii_mm[r0 + i] : 0.0;
+                rr.w[i] = i < nr ? ee_bar[r0 + i] : 0.0;
+            }
+            hipLaunchKernelGGL(ee_adjoint_kernel<T>, grid, block, 0, st, rows, cols, df, rr, nr, cell, acc, static_cast<T*>(mtf_bar), mtf_bar_ld);
+            acc = 1;
+            r0 += kEeMaxRadii;
+        } while (r0 < nradii);
+        return int(hipGetLastError());
+    });
 }
 
 }  // extern "C"

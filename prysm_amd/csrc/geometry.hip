@@ -20,8 +20,6 @@
 // the numpy walk of the same table (geometry_plan.evaluate) does the same arithmetic.  No LDS, no atomics.
 #include <cmath>
 
-#include "pm_internal.h"
-
 #include "pm_entry.h"
 
 namespace pm {
@@ -353,8 +351,6 @@ __global__ __launch_bounds__(kThreads) void polar_to_cart_kernel(int64_t n, cons
     y[i] = rho[i] * s;
 }
 
-bool real_dtype(int32_t dtype) { return dtype == PM_F32 || dtype == PM_F64; }
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 int64_t blocks_of(int64_t n) { return (n + kThreads - 1) / kThreads; }
 
 template <typename T, typename O>
@@ -373,19 +369,19 @@ void launch_render(int32_t coords, int64_t ny, int64_t nx, const void* x, const 
                    const void* table, int nsteps, int64_t batch, int32_t out_kind, double aa_dx, void* out, int64_t out_ld, int64_t out_bstride,
                    hipStream_t st) {
     RenderArgs<T> a;
-    a.ny = ny, a.nx = nx, a.x = (const T*)x, a.y = (const T*)y, a.ox = ox, a.oy = oy, a.dx = T(dx), a.dy = T(dy);
-    a.table = (const GStep<T>*)table, a.nsteps = nsteps, a.out_kind = out_kind, a.aa_dx = T(aa_dx);
+    a.ny = ny, a.nx = nx, a.x = static_cast<const T*>(x), a.y = static_cast<const T*>(y), a.ox = ox, a.oy = oy, a.dx = T(dx), a.dy = T(dy);
+    a.table = static_cast<const GStep<T>*>(table), a.nsteps = nsteps, a.out_kind = out_kind, a.aa_dx = T(aa_dx);
     a.out = out, a.out_ld = out_ld, a.out_bstride = out_bstride;
     a.tiles_per_row = (nx + kTileX - 1) / kTileX;
     // 16-byte pieces: every row of every array starts on a 16-byte boundary (4 bytes for the mask's 4-byte pieces)
     const size_t es = sizeof(T);
     a.vec_in = coords == PM_COORDS_GRID ? 0
-               : coords == PM_COORDS_SEPARABLE ? aligned16(x)
-                                               : (aligned16(x) && aligned16(y) && (nx * es) % 16 == 0);
+               : coords == PM_COORDS_SEPARABLE ? aligned(x, 16)
+                                               : (aligned(x, 16) && aligned(y, 16) && (nx * es) % 16 == 0);
     if (out_kind == PM_SDF_MASK)
-        a.vec_out = reinterpret_cast<uintptr_t>(out) % 4 == 0 && out_ld % 4 == 0 && out_bstride % 4 == 0;
+        a.vec_out = aligned(out, 4) && out_ld % 4 == 0 && out_bstride % 4 == 0;
     else
-        a.vec_out = aligned16(out) && (out_ld * es) % 16 == 0 && (out_bstride * es) % 16 == 0;
+        a.vec_out = aligned(out, 16) && (out_ld * es) % 16 == 0 && (out_bstride * es) % 16 == 0;
     const int64_t tiles = ny * a.tiles_per_row;
     const dim3 grid{unsigned((tiles + kWaves - 1) / kWaves), unsigned(batch)};
     if (out_kind == PM_SDF_MASK)
@@ -407,13 +403,12 @@ int pm_xy_grid(int32_t dtype, int64_t ny, int64_t nx, double dx, int32_t grid, v
     const int64_t n = grid ? ny * nx : std::max(ny, nx);
     if (ny > INT32_MAX || nx > INT32_MAX || blocks_of(n) > INT32_MAX) return fail(PM_ERR_ARG, "pm_xy_grid: %lld x %lld is too large", (long long)ny, (long long)nx);
     if (n == 0) return 0;
-    hipStream_t st = PM_STREAM(stream);
-    const dim3 g{unsigned(blocks_of(n))}, b{kThreads};
-    if (dtype == PM_F32)
-        hipLaunchKernelGGL(xy_grid_kernel<float>, g, b, 0, st, ny, nx, float(dx), grid != 0, (float*)x, (float*)y);
-    else
-        hipLaunchKernelGGL(xy_grid_kernel<double>, g, b, 0, st, ny, nx, dx, grid != 0, (double*)x, (double*)y);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_xy_grid", [&](auto real) {
+        using T = decltype(real);
+        hipLaunchKernelGGL(xy_grid_kernel<T>, dim3(unsigned(blocks_of(n))), dim3(kThreads), 0, PM_STREAM(stream), ny, nx, T(dx), grid != 0,
+                           static_cast<T*>(x), static_cast<T*>(y));
+        return int(hipGetLastError());
+    });
 }
 
 int pm_cart_to_polar(int32_t dtype, int64_t ny, int64_t nx, int32_t separable, const void* x, const void* y, void* rho, void* phi, void* stream) {
@@ -422,14 +417,12 @@ int pm_cart_to_polar(int32_t dtype, int64_t ny, int64_t nx, int32_t separable, c
     if (ny > INT32_MAX || nx > INT32_MAX || blocks_of(ny * nx) > INT32_MAX)
         return fail(PM_ERR_ARG, "pm_cart_to_polar: %lld x %lld is too large", (long long)ny, (long long)nx);
     if (ny * nx == 0) return 0;
-    hipStream_t st = PM_STREAM(stream);
-    const dim3 g{unsigned(blocks_of(ny * nx))}, b{kThreads};
-    if (dtype == PM_F32)
-        hipLaunchKernelGGL(cart_to_polar_kernel<float>, g, b, 0, st, ny, nx, separable != 0, (const float*)x, (const float*)y, (float*)rho, (float*)phi);
-    else
-        hipLaunchKernelGGL(cart_to_polar_kernel<double>, g, b, 0, st, ny, nx, separable != 0, (const double*)x, (const double*)y, (double*)rho,
-                           (double*)phi);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_cart_to_polar", [&](auto real) {
+        using T = decltype(real);
+        hipLaunchKernelGGL(cart_to_polar_kernel<T>, dim3(unsigned(blocks_of(ny * nx))), dim3(kThreads), 0, PM_STREAM(stream), ny, nx,
+                           separable != 0, static_cast<const T*>(x), static_cast<const T*>(y), static_cast<T*>(rho), static_cast<T*>(phi));
+        return int(hipGetLastError());
+    });
 }
 
 int pm_polar_to_cart(int32_t dtype, int64_t n, const void* rho, const void* phi, void* x, void* y, void* stream) {
@@ -437,13 +430,12 @@ int pm_polar_to_cart(int32_t dtype, int64_t n, const void* rho, const void* phi,
     if (n < 0 || !rho || !phi || !x || !y) return fail(PM_ERR_ARG, "pm_polar_to_cart: bad argument (null pointer or negative size)");
     if (blocks_of(n) > INT32_MAX) return fail(PM_ERR_ARG, "pm_polar_to_cart: %lld points is too many", (long long)n);
     if (n == 0) return 0;
-    hipStream_t st = PM_STREAM(stream);
-    const dim3 g{unsigned(blocks_of(n))}, b{kThreads};
-    if (dtype == PM_F32)
-        hipLaunchKernelGGL(polar_to_cart_kernel<float>, g, b, 0, st, n, (const float*)rho, (const float*)phi, (float*)x, (float*)y);
-    else
-        hipLaunchKernelGGL(polar_to_cart_kernel<double>, g, b, 0, st, n, (const double*)rho, (const double*)phi, (double*)x, (double*)y);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_polar_to_cart", [&](auto real) {
+        using T = decltype(real);
+        hipLaunchKernelGGL(polar_to_cart_kernel<T>, dim3(unsigned(blocks_of(n))), dim3(kThreads), 0, PM_STREAM(stream), n,
+                           static_cast<const T*>(rho), static_cast<const T*>(phi), static_cast<T*>(x), static_cast<T*>(y));
+        return int(hipGetLastError());
+    });
 }
 
 int pm_sdf_render(int32_t dtype, int32_t coords, int64_t ny, int64_t nx, const void* x, const void* y, int64_t ox, int64_t oy, double dx,
@@ -462,18 +454,17 @@ int pm_sdf_render(int32_t dtype, int32_t coords, int64_t ny, int64_t nx, const v
     if (out_kind == PM_SDF_COVERAGE && !(std::isfinite(aa_dx) && aa_dx > 0))
         return fail(PM_ERR_ARG, "pm_sdf_render: coverage needs a sample spacing aa_dx > 0");
     if (out_ld < nx) return fail(PM_ERR_ARG, "pm_sdf_render: out_ld %lld is smaller than the row of %lld", (long long)out_ld, (long long)nx);
-    if (batch > 1 && out_bstride < ny * out_ld) return fail(PM_ERR_ARG, "pm_sdf_render: out_bstride: the outputs of a stack would overlap");
+    if (!stack_ok(batch, ny, out_ld, out_bstride)) return fail(PM_ERR_ARG, "pm_sdf_render: out_bstride: the outputs of a stack would overlap");
     if (nsteps > INT32_MAX || batch > 65535) return fail(PM_ERR_ARG, "pm_sdf_render: too many steps or programs (batch <= 65535)");
     const int64_t tpr = (nx + kTileX - 1) / kTileX;
     if (nx > INT32_MAX || ny > INT32_MAX || (ny * tpr + kWaves - 1) / kWaves > INT32_MAX)
         return fail(PM_ERR_ARG, "pm_sdf_render: %lld x %lld is too large", (long long)ny, (long long)nx);
     if (ny == 0 || nx == 0 || batch == 0) return 0;
-    hipStream_t st = PM_STREAM(stream);
-    if (dtype == PM_F32)
-        launch_render<float>(coords, ny, nx, x, y, ox, oy, dx, dy, table, int(nsteps), batch, out_kind, aa_dx, out, out_ld, out_bstride, st);
-    else
-        launch_render<double>(coords, ny, nx, x, y, ox, oy, dx, dy, table, int(nsteps), batch, out_kind, aa_dx, out, out_ld, out_bstride, st);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_sdf_render", [&](auto real) {
+        launch_render<decltype(real)>(coords, ny, nx, x, y, ox, oy, dx, dy, table, int(nsteps), batch, out_kind, aa_dx, out, out_ld, out_bstride,
+                                      PM_STREAM(stream));
+        return int(hipGetLastError());
+    });
 }
 
 }  // extern "C"

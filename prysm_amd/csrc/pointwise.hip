@@ -2,35 +2,13 @@
 //
 // All of them are 2-D row-major with a leading dimension.  One thread handles ONE element at a time: a thread owns a column (64
 // adjacent columns per wavefront, so a row is read and written in whole lines) and strides over the rows, 64 x 4 threads per workgroup
-// and at most 65535 workgroups down the rows.  That loop is written once (sweep_kernel); each operation is a named functor with a
+// and at most 65535 workgroups down the rows.  That loop is written once (pm_sweep.h); each operation is a named functor with a
 // per-column part and a per-point part.  Phases are reduced in fp64 before the sincos so the fp32 path keeps full fp32 accuracy for
 // arguments of many thousands of radians (quadratic phases, OPD / lambda).
 #include "pm_entry.h"
+#include "pm_sweep.h"
 
 namespace pm {
-
-// ---------------------------------------------------------------- the row sweep
-// F::column(c) is evaluated once per thread (what an operation hoists out of the row loop; NoColumn where there is nothing),
-// F::point(r, c, column) once per element.  More than 4 * 65535 rows are reached by the grid-stride step.
-struct NoColumn {};
-
-template <typename F>
-__global__ void sweep_kernel(int64_t rows, int64_t cols, const F f) {
-    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    const auto col = f.column(c);
-    for (int64_t r = int64_t(blockIdx.y) * blockDim.y + threadIdx.y; r < rows; r += int64_t(gridDim.y) * blockDim.y) f.point(r, c, col);
-}
-
-template <typename F>
-static int sweep(int64_t rows, int64_t cols, hipStream_t st, const F& f) {
-    const dim3 block(64, 4);
-    const int64_t gx = (cols + block.x - 1) / block.x;
-    int64_t gy = (rows + block.y - 1) / block.y;
-    if (gy > 65535) gy = 65535;
-    hipLaunchKernelGGL(sweep_kernel<F>, dim3((unsigned)gx, (unsigned)gy), block, 0, st, rows, cols, f);
-    return int(hipGetLastError());
-}
 
 __device__ __forceinline__ void sincos_turns(double turns, double* s, double* c) {
     // exp(2 pi i turns): reduce to [-0.5, 0.5) turns exactly, then sincospi

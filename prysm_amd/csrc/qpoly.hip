@@ -11,18 +11,13 @@
 // Im z^|m| need no trigonometry in the loop.  Radial tables (Qbfs, Qcon) take PM_QPOLY_RADIAL points: u only, no angle read.  The
 // step index is uniform, so the table is read through the scalar cache.  A step whose slot is outside [0, nmodes) writes nothing.
 //
-// The tile, its 16-byte loads and stores, the wave reduction and the fixed-order second stage are zernike_walk.h's; the projection is
-// pm_zernike_project's scheme: per-workgroup partials in the caller's workspace, then a fixed-order sum.  No atomics, so every run and
-// every graph replay gives the same bits.
+// The tile, its 16-byte loads and stores, the wave reduction, the fixed-order second stage and the host's launch helpers are
+// zernike_walk.h's; the projection is pm_zernike_project's scheme: per-workgroup partials in the caller's workspace, then a
+// fixed-order sum.  No atomics, so every run and every graph replay gives the same bits.
 #include "zernike_walk.h"
-
-#include "pm_entry.h"
 
 namespace pm {
 namespace {
-
-constexpr int kMaxProjectGroups = 1024;                 // workgroups of a projection (grid-stride beyond): the partial count per output
-constexpr size_t kProjectLds = 64 * 1024;               // per-wave accumulators of a projection workgroup
 
 enum { QS_RESET = 1, QS_SEED = 2, QS_ADV = 4 };
 enum { QP_NONE = 0, QP_BFS = 1, QP_CON = 2, QP_COS = 3, QP_SIN = 4 };
@@ -245,30 +240,9 @@ __global__ __launch_bounds__(kThreads) void qpoly_project_kernel(int64_t npts, i
     }
 }
 
-size_t elem_of(int32_t dtype) { return dtype == PM_F32 ? 4 : 8; }
-
-// 16-byte vectors: every plane of npts points starts on a 16-byte boundary, and so does every pointer given (null: not read)
-int vec_ok(int64_t npts, std::initializer_list<const void*> ptrs) {
-    if (npts % kVec) return 0;
-    for (const void* p : ptrs)
-        if (reinterpret_cast<uintptr_t>(p) % 16) return 0;
-    return 1;
-}
-
-int64_t tiles_of(int64_t npts) { return (npts + int64_t(kThreads) * kVec - 1) / (int64_t(kThreads) * kVec); }
-
-int64_t project_groups(int64_t npts) { return std::max<int64_t>(1, std::min<int64_t>(tiles_of(npts), kMaxProjectGroups)); }
-
-// the largest of 8, 4, 2, 1 coefficient vectors per projection walk whose per-wave accumulators fit kProjectLds
-int project_nb(int32_t dtype, int64_t nmodes, int64_t batch) {
-    for (int nb = 8; nb > 1; nb >>= 1)
-        if (nb <= batch && size_t(kWaves) * nb * size_t(nmodes) * elem_of(dtype) <= kProjectLds) return nb;
-    return 1;
-}
-
 int check_walk(const char* who, int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
                int64_t nmodes) {
-    if (dtype != PM_F32 && dtype != PM_F64) return fail(PM_ERR_ARG, "%s: dtype must be PM_F32 or PM_F64", who);
+    if (!real_dtype(dtype)) return fail(PM_ERR_ARG, "%s: dtype must be PM_F32 or PM_F64", who);
     if (coords != PM_ZERNIKE_CARTESIAN && coords != PM_ZERNIKE_POLAR && coords != PM_QPOLY_RADIAL)
         return fail(PM_ERR_ARG, "%s: coords must be PM_ZERNIKE_CARTESIAN, PM_ZERNIKE_POLAR or PM_QPOLY_RADIAL", who);
     if (!u || (!v && coords != PM_QPOLY_RADIAL) || !table || npts < 0 || nsteps < 0 || nmodes < 0 || nsteps > INT32_MAX ||
@@ -276,60 +250,6 @@ int check_walk(const char* who, int32_t dtype, int32_t coords, int64_t npts, con
         return fail(PM_ERR_ARG, "%s: bad argument (null pointer or negative size)", who);
     if (tiles_of(npts) > INT32_MAX) return fail(PM_ERR_ARG, "%s: %lld points is too many", who, (long long)npts);
     return 0;
-}
-
-template <typename T>
-void launch_basis(int64_t npts, int coords, const void* u, const void* v, const void* table, int nsteps, int nmodes, void* out, hipStream_t st) {
-    const dim3 grid{unsigned(tiles_of(npts))}, block{kThreads};
-    const int vec = vec_ok(npts, {u, v, out});
-    hipLaunchKernelGGL(qpoly_basis_kernel<T>, grid, block, 0, st, npts, coords, (const T*)u, (const T*)v, (const QStep<T>*)table, nsteps,
-                       nmodes, (T*)out, vec);
-}
-
-template <typename T>
-void launch_sum(int64_t npts, int coords, const void* u, const void* v, const void* table, int nsteps, int nmodes, int64_t batch,
-                const void* coefs, int accumulate, void* out, hipStream_t st) {
-    const dim3 grid{unsigned(tiles_of(npts))}, block{kThreads};
-    const int vec = vec_ok(npts, {u, v, out});
-    for (int64_t b0 = 0; b0 < batch;) {
-        const int64_t left = batch - b0;
-        const T* c = (const T*)coefs + b0 * nmodes;
-        T* o = (T*)out + b0 * npts;
-#define PM_QSUM(NB)                                                                                                                  \
-    hipLaunchKernelGGL((qpoly_sum_kernel<T, NB>), grid, block, 0, st, npts, coords, (const T*)u, (const T*)v, (const QStep<T>*)table, \
-                       nsteps, nmodes, c, accumulate, o, vec);                                                                          \
-    b0 += NB
-        if (left >= 8) { PM_QSUM(8); }
-        else if (left >= 4) { PM_QSUM(4); }
-        else if (left >= 2) { PM_QSUM(2); }
-        else { PM_QSUM(1); }
-#undef PM_QSUM
-    }
-}
-
-template <typename T>
-void launch_project(int64_t npts, int coords, const void* u, const void* v, const void* table, int nsteps, int nmodes, int64_t batch,
-                    const void* g, void* out, void* ws, int nb, hipStream_t st) {
-    const int64_t groups = project_groups(npts);
-    const dim3 grid{unsigned(groups)}, block{kThreads};
-    T* partial = (T*)ws;
-    const int vec = vec_ok(npts, {u, v, g});
-    for (int64_t b0 = 0; b0 < batch;) {
-        const int64_t left = batch - b0;
-        const T* gb = (const T*)g + b0 * npts;
-        T* pb = partial + b0 * nmodes;
-#define PM_QPROJ(NB)                                                                                                                \
-    hipLaunchKernelGGL((qpoly_project_kernel<T, NB>), grid, block, size_t(kWaves) * NB * nmodes * sizeof(T), st, npts, coords,       \
-                       (const T*)u, (const T*)v, (const QStep<T>*)table, nsteps, nmodes, gb, pb, batch * nmodes, vec);                      \
-    b0 += NB
-        if (nb >= 8 && left >= 8) { PM_QPROJ(8); }
-        else if (nb >= 4 && left >= 4) { PM_QPROJ(4); }
-        else if (nb >= 2 && left >= 2) { PM_QPROJ(2); }
-        else { PM_QPROJ(1); }
-#undef PM_QPROJ
-    }
-    hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(batch * nmodes)), block, 0, st, groups, batch * nmodes, (const T*)partial,
-                       (T*)out);
 }
 
 }  // namespace
@@ -344,12 +264,13 @@ int pm_qpoly_basis(int32_t dtype, int32_t coords, int64_t npts, const void* u, c
     if (int rc = check_walk("pm_qpoly_basis", dtype, coords, npts, u, v, table, nsteps, nmodes)) return rc;
     if (!out) return fail(PM_ERR_ARG, "pm_qpoly_basis: bad argument (null pointer)");
     if (npts == 0 || nmodes == 0) return 0;
-    hipStream_t st = PM_STREAM(stream);
-    if (dtype == PM_F32)
-        launch_basis<float>(npts, coords, u, v, table, int(nsteps), int(nmodes), out, st);
-    else
-        launch_basis<double>(npts, coords, u, v, table, int(nsteps), int(nmodes), out, st);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_qpoly_basis", [&](auto real) {
+        using T = decltype(real);
+        hipLaunchKernelGGL(qpoly_basis_kernel<T>, dim3(unsigned(tiles_of(npts))), dim3(kThreads), 0, PM_STREAM(stream), npts, coords,
+                           static_cast<const T*>(u), static_cast<const T*>(v), static_cast<const QStep<T>*>(table), int(nsteps), int(nmodes),
+                           static_cast<T*>(out), vec_ok(npts, {u, v, out}));
+        return int(hipGetLastError());
+    });
 }
 
 int pm_qpoly_sum(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
@@ -357,16 +278,24 @@ int pm_qpoly_sum(int32_t dtype, int32_t coords, int64_t npts, const void* u, con
     if (int rc = check_walk("pm_qpoly_sum", dtype, coords, npts, u, v, table, nsteps, nmodes)) return rc;
     if (!out || !coefs || batch < 0) return fail(PM_ERR_ARG, "pm_qpoly_sum: bad argument (null pointer or negative batch)");
     if (npts == 0 || batch == 0) return 0;
-    hipStream_t st = PM_STREAM(stream);
-    if (dtype == PM_F32)
-        launch_sum<float>(npts, coords, u, v, table, int(nsteps), int(nmodes), batch, coefs, accumulate != 0, out, st);
-    else
-        launch_sum<double>(npts, coords, u, v, table, int(nsteps), int(nmodes), batch, coefs, accumulate != 0, out, st);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_qpoly_sum", [&](auto real) {
+        using T = decltype(real);
+        const T *up = static_cast<const T*>(u), *vp = static_cast<const T*>(v), *c = static_cast<const T*>(coefs);
+        const QStep<T>* steps = static_cast<const QStep<T>*>(table);
+        T* o = static_cast<T*>(out);
+        const dim3 grid{unsigned(tiles_of(npts))}, block{kThreads};
+        const int vec = vec_ok(npts, {u, v, out});
+        for (int64_t b0 = 0; b0 < batch;)
+            b0 += by_nb(batch - b0, 8, [&](auto nb) {
+                hipLaunchKernelGGL((qpoly_sum_kernel<T, decltype(nb)::value>), grid, block, 0, PM_STREAM(stream), npts, coords, up, vp, steps,
+                                   int(nsteps), int(nmodes), c + b0 * nmodes, accumulate != 0, o + b0 * npts, vec);
+            });
+        return int(hipGetLastError());
+    });
 }
 
 size_t pm_qpoly_project_workspace(int32_t dtype, int64_t npts, int64_t nmodes, int64_t batch) {
-    if ((dtype != PM_F32 && dtype != PM_F64) || npts < 0 || nmodes < 0 || batch < 0) return 0;
+    if (!real_dtype(dtype) || npts < 0 || nmodes < 0 || batch < 0) return 0;
     return size_t(project_groups(npts)) * size_t(batch) * size_t(nmodes) * elem_of(dtype);
 }
 
@@ -375,20 +304,30 @@ int pm_qpoly_project(int32_t dtype, int32_t coords, int64_t npts, const void* u,
     if (int rc = check_walk("pm_qpoly_project", dtype, coords, npts, u, v, table, nsteps, nmodes)) return rc;
     if (!out || !databar || batch < 0) return fail(PM_ERR_ARG, "pm_qpoly_project: bad argument (null pointer or negative batch)");
     if (batch * nmodes > INT32_MAX) return fail(PM_ERR_ARG, "pm_qpoly_project: batch * nmodes is too large");
-    if (size_t(kWaves) * size_t(nmodes) * elem_of(dtype) > kProjectLds)
+    if (project_lds(1, nmodes, elem_of(dtype)) > kProjectLds)
         return fail(PM_ERR_UNSUPPORTED, "pm_qpoly_project: %lld modes do not fit the workgroup's accumulators", (long long)nmodes);
     if (batch == 0 || nmodes == 0) return 0;
     const size_t need = pm_qpoly_project_workspace(dtype, npts, nmodes, batch);
     if (!workspace || workspace_bytes < need)
         return fail(PM_ERR_WORKSPACE, "pm_qpoly_project: workspace of %zu bytes is smaller than the %zu pm_qpoly_project_workspace asks for",
                     workspace_bytes, need);
-    hipStream_t st = PM_STREAM(stream);
-    const int nb = project_nb(dtype, nmodes, batch);
-    if (dtype == PM_F32)
-        launch_project<float>(npts, coords, u, v, table, int(nsteps), int(nmodes), batch, databar, out, workspace, nb, st);
-    else
-        launch_project<double>(npts, coords, u, v, table, int(nsteps), int(nmodes), batch, databar, out, workspace, nb, st);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_qpoly_project", [&](auto real) {
+        using T = decltype(real);
+        const T *up = static_cast<const T*>(u), *vp = static_cast<const T*>(v), *g = static_cast<const T*>(databar);
+        const QStep<T>* steps = static_cast<const QStep<T>*>(table);
+        T* partial = static_cast<T*>(workspace);
+        hipStream_t st = PM_STREAM(stream);
+        const int64_t groups = project_groups(npts), nout = batch * nmodes;
+        const dim3 grid{unsigned(groups)}, block{kThreads};
+        const int vec = vec_ok(npts, {u, v, databar});
+        for (int64_t b0 = 0; b0 < batch;)
+            b0 += by_nb(batch - b0, project_nb(dtype, nmodes, batch), [&](auto nb) {
+                hipLaunchKernelGGL((qpoly_project_kernel<T, decltype(nb)::value>), grid, block, project_lds(nb, nmodes, sizeof(T)), st, npts,
+                                   coords, up, vp, steps, int(nsteps), int(nmodes), g + b0 * npts, partial + b0 * nmodes, nout, vec);
+            });
+        hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(nout)), block, 0, st, groups, nout, partial, static_cast<T*>(out));
+        return int(hipGetLastError());
+    });
 }
 
 }  // extern "C"

@@ -16,13 +16,10 @@
 // prysm_amd/segmented.py and checked by pm_segment_plan_check before it is uploaded.
 #include "zernike_walk.h"
 
-#include "pm_entry.h"
-
 namespace pm {
 namespace {
 
 constexpr int kSegGroups = 256;                          // workgroups per segment of a projection (grid-stride beyond)
-constexpr size_t kSegLds = 64 * 1024;                    // per-wave accumulators of a projection workgroup
 
 // one segment of the plan (prysm_amd/segmented.py: _DESC_DTYPE)
 struct SegDesc {
@@ -233,29 +230,9 @@ __global__ __launch_bounds__(kThreads) void segment_project_kernel(int rows, int
     }
 }
 
-size_t elem_of(int32_t dtype) { return dtype == PM_F32 ? 4 : 8; }
-
-int64_t seg_groups(int64_t window_pts) {
-    const int64_t tiles = (window_pts + int64_t(kThreads) * kVec - 1) / (int64_t(kThreads) * kVec);
-    return std::max<int64_t>(1, std::min<int64_t>(tiles, kSegGroups));
-}
-
-int seg_nb(int32_t dtype, int64_t nmodes, int64_t batch) {
-    for (int nb = 8; nb > 1; nb >>= 1)
-        if (nb <= batch && size_t(kWaves) * nb * size_t(nmodes) * elem_of(dtype) <= kSegLds) return nb;
-    return 1;
-}
-
-int vec_ok(int64_t npts, std::initializer_list<const void*> ptrs) {
-    if (npts % kVec) return 0;
-    for (const void* p : ptrs)
-        if (reinterpret_cast<uintptr_t>(p) % 16) return 0;
-    return 1;
-}
-
 int check_common(const char* who, int32_t dtype, int32_t source, int64_t rows, int64_t cols, const void* x, const void* y, int64_t nseg,
                  const void* plan, const void* masks, const void* table, int64_t nsteps, int64_t nmodes, const void* basis, int64_t batch) {
-    if (dtype != PM_F32 && dtype != PM_F64) return fail(PM_ERR_ARG, "%s: dtype must be PM_F32 or PM_F64", who);
+    if (!real_dtype(dtype)) return fail(PM_ERR_ARG, "%s: dtype must be PM_F32 or PM_F64", who);
     if (source != PM_SEGMENT_ZERNIKE && source != PM_SEGMENT_STORED)
         return fail(PM_ERR_ARG, "%s: source must be PM_SEGMENT_ZERNIKE or PM_SEGMENT_STORED", who);
     if (rows < 0 || cols < 0 || nseg < 0 || nmodes < 0 || batch < 0 || nsteps < 0)
@@ -270,53 +247,11 @@ int check_common(const char* who, int32_t dtype, int32_t source, int64_t rows, i
     return 0;
 }
 
-template <int SRC, typename T>
-void launch_compose(int rows, int cols, const void* x, const void* y, int nseg, const void* plan, const void* masks, int ncover,
-                    const void* cover, const void* table, int nsteps, int nmodes, const void* basis, int64_t batch, const void* coefs,
-                    int accumulate, void* out, hipStream_t st) {
-    const int64_t npts = int64_t(rows) * cols;
-    const dim3 grid{unsigned((npts + int64_t(kThreads) * kVec - 1) / (int64_t(kThreads) * kVec))}, block{kThreads};
-    const int vec = vec_ok(npts, {out});
-    for (int64_t b0 = 0; b0 < batch;) {
-        const int64_t left = batch - b0;
-        const T* c = (const T*)coefs + b0 * nseg * nmodes;
-        T* o = (T*)out + b0 * npts;
-#define PM_SCOMP(NB)                                                                                                                     \
-    hipLaunchKernelGGL((segment_compose_kernel<SRC, T, NB>), grid, block, 0, st, rows, cols, (const T*)x, (const T*)y, nseg,               \
-                       (const SegDesc*)plan, (const T*)masks, ncover, (const int16_t*)cover, (const ZStep<T>*)table, nsteps, nmodes,        \
-                       (const T*)basis, c, accumulate, o, vec);                                                                             \
-    b0 += NB
-        if (left >= 8) { PM_SCOMP(8); }
-        else if (left >= 4) { PM_SCOMP(4); }
-        else if (left >= 2) { PM_SCOMP(2); }
-        else { PM_SCOMP(1); }
-#undef PM_SCOMP
-    }
-}
-
-template <int SRC, typename T>
-void launch_project(int rows, int cols, const void* x, const void* y, int nseg, const void* plan, const void* masks, int64_t window_pts,
-                    const void* table, int nsteps, int nmodes, const void* basis, int64_t batch, const void* g, void* out, void* ws, int nb,
-                    hipStream_t st) {
-    const int64_t groups = seg_groups(window_pts), npts = int64_t(rows) * cols, ld = batch * nseg * nmodes;
-    const dim3 grid{unsigned(groups), unsigned(nseg)}, block{kThreads};
-    T* partial = (T*)ws;
-    for (int64_t b0 = 0; b0 < batch;) {
-        const int64_t left = batch - b0;
-        const T* gb = (const T*)g + b0 * npts;
-        T* pb = partial + b0 * nseg * nmodes;
-#define PM_SPROJ(NB)                                                                                                                     \
-    hipLaunchKernelGGL((segment_project_kernel<SRC, T, NB>), grid, block, size_t(kWaves) * NB * nmodes * sizeof(T), st, rows, cols,        \
-                       (const T*)x, (const T*)y, nseg, (const SegDesc*)plan, (const T*)masks, (const ZStep<T>*)table, nsteps, nmodes,       \
-                       (const T*)basis, gb, pb, ld);                                                                                        \
-    b0 += NB
-        if (nb >= 8 && left >= 8) { PM_SPROJ(8); }
-        else if (nb >= 4 && left >= 4) { PM_SPROJ(4); }
-        else if (nb >= 2 && left >= 2) { PM_SPROJ(2); }
-        else { PM_SPROJ(1); }
-#undef PM_SPROJ
-    }
-    hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(ld)), block, 0, st, groups, ld, (const T*)partial, (T*)out);
+// calls f with the source of Z_{s,k} (checked before) as a std::integral_constant, the template parameter of both kernels
+template <typename F>
+int by_source(int32_t source, F&& f) {
+    if (source == PM_SEGMENT_ZERNIKE) return f(std::integral_constant<int, PM_SEGMENT_ZERNIKE>{});
+    return f(std::integral_constant<int, PM_SEGMENT_STORED>{});
 }
 
 }  // namespace
@@ -358,24 +293,31 @@ int pm_segment_compose(int32_t dtype, int32_t source, int64_t rows, int64_t cols
     if (!out || !coefs || ncover < 0 || ncover > nseg || (ncover && !cover))
         return fail(PM_ERR_ARG, "pm_segment_compose: bad argument (null out, coefs or cover, or ncover outside [0, nseg])");
     if (rows * cols == 0 || batch == 0) return 0;
-    hipStream_t st = PM_STREAM(stream);
-    const bool zern = source == PM_SEGMENT_ZERNIKE;
-#define PM_SC_ARGS int(rows), int(cols), x, y, int(nseg), plan, masks, int(ncover), cover, table, int(nsteps), int(nmodes), basis, batch, coefs, \
-                   accumulate != 0, out, st
-    if (dtype == PM_F32) {
-        if (zern) launch_compose<PM_SEGMENT_ZERNIKE, float>(PM_SC_ARGS);
-        else launch_compose<PM_SEGMENT_STORED, float>(PM_SC_ARGS);
-    } else {
-        if (zern) launch_compose<PM_SEGMENT_ZERNIKE, double>(PM_SC_ARGS);
-        else launch_compose<PM_SEGMENT_STORED, double>(PM_SC_ARGS);
-    }
-#undef PM_SC_ARGS
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_segment_compose", [&](auto real) {
+        return by_source(source, [&](auto src) {
+            using T = decltype(real);
+            const T *xp = static_cast<const T*>(x), *yp = static_cast<const T*>(y), *mp = static_cast<const T*>(masks);
+            const T *bp = static_cast<const T*>(basis), *c = static_cast<const T*>(coefs);
+            const ZStep<T>* steps = static_cast<const ZStep<T>*>(table);
+            T* o = static_cast<T*>(out);
+            const int64_t npts = rows * cols;
+            const dim3 grid{unsigned(tiles_of(npts))}, block{kThreads};
+            const int vec = vec_ok(npts, {out});
+            for (int64_t b0 = 0; b0 < batch;)
+                b0 += by_nb(batch - b0, 8, [&](auto nb) {
+                    hipLaunchKernelGGL((segment_compose_kernel<decltype(src)::value, T, decltype(nb)::value>), grid, block, 0, PM_STREAM(stream),
+                                       int(rows), int(cols), xp, yp, int(nseg), static_cast<const SegDesc*>(plan), mp, int(ncover),
+                                       static_cast<const int16_t*>(cover), steps, int(nsteps), int(nmodes), bp, c + b0 * nseg * nmodes,
+                                       accumulate != 0, o + b0 * npts, vec);
+                });
+            return int(hipGetLastError());
+        });
+    });
 }
 
 size_t pm_segment_project_workspace(int32_t dtype, int64_t window_pts, int64_t nseg, int64_t nmodes, int64_t batch) {
-    if ((dtype != PM_F32 && dtype != PM_F64) || window_pts < 0 || nseg < 0 || nmodes < 0 || batch < 0) return 0;
-    return size_t(seg_groups(window_pts)) * size_t(batch) * size_t(nseg) * size_t(nmodes) * elem_of(dtype);
+    if (!real_dtype(dtype) || window_pts < 0 || nseg < 0 || nmodes < 0 || batch < 0) return 0;
+    return size_t(project_groups(window_pts, kSegGroups)) * size_t(batch) * size_t(nseg) * size_t(nmodes) * elem_of(dtype);
 }
 
 int pm_segment_project(int32_t dtype, int32_t source, int64_t rows, int64_t cols, const void* x, const void* y, int64_t nseg, const void* plan,
@@ -386,27 +328,34 @@ int pm_segment_project(int32_t dtype, int32_t source, int64_t rows, int64_t cols
     if (!out || !databar || window_pts < 0 || window_pts > rows * cols)
         return fail(PM_ERR_ARG, "pm_segment_project: bad argument (null out or databar, or window_pts outside [0, rows * cols])");
     if (batch * nseg * nmodes > INT32_MAX) return fail(PM_ERR_ARG, "pm_segment_project: batch * nseg * nmodes is too large");
-    if (size_t(kWaves) * size_t(nmodes) * elem_of(dtype) > kSegLds)
+    if (project_lds(1, nmodes, elem_of(dtype)) > kProjectLds)
         return fail(PM_ERR_UNSUPPORTED, "pm_segment_project: %lld modes do not fit the workgroup's accumulators", (long long)nmodes);
     if (batch == 0 || nseg == 0 || nmodes == 0) return 0;
     const size_t need = pm_segment_project_workspace(dtype, window_pts, nseg, nmodes, batch);
     if (!workspace || workspace_bytes < need)
         return fail(PM_ERR_WORKSPACE, "pm_segment_project: workspace of %zu bytes is smaller than the %zu pm_segment_project_workspace asks for",
                     workspace_bytes, need);
-    hipStream_t st = PM_STREAM(stream);
-    const bool zern = source == PM_SEGMENT_ZERNIKE;
-    const int nb = seg_nb(dtype, nmodes, batch);
-#define PM_SP_ARGS int(rows), int(cols), x, y, int(nseg), plan, masks, window_pts, table, int(nsteps), int(nmodes), basis, batch, databar, out, \
-                   workspace, nb, st
-    if (dtype == PM_F32) {
-        if (zern) launch_project<PM_SEGMENT_ZERNIKE, float>(PM_SP_ARGS);
-        else launch_project<PM_SEGMENT_STORED, float>(PM_SP_ARGS);
-    } else {
-        if (zern) launch_project<PM_SEGMENT_ZERNIKE, double>(PM_SP_ARGS);
-        else launch_project<PM_SEGMENT_STORED, double>(PM_SP_ARGS);
-    }
-#undef PM_SP_ARGS
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_segment_project", [&](auto real) {
+        return by_source(source, [&](auto src) {
+            using T = decltype(real);
+            const T *xp = static_cast<const T*>(x), *yp = static_cast<const T*>(y), *mp = static_cast<const T*>(masks);
+            const T *bp = static_cast<const T*>(basis), *g = static_cast<const T*>(databar);
+            const ZStep<T>* steps = static_cast<const ZStep<T>*>(table);
+            T* partial = static_cast<T*>(workspace);
+            hipStream_t st = PM_STREAM(stream);
+            const int64_t groups = project_groups(window_pts, kSegGroups), npts = rows * cols, ld = batch * nseg * nmodes;
+            const dim3 grid{unsigned(groups), unsigned(nseg)}, block{kThreads};
+            for (int64_t b0 = 0; b0 < batch;)
+                b0 += by_nb(batch - b0, project_nb(dtype, nmodes, batch), [&](auto nb) {
+                    hipLaunchKernelGGL((segment_project_kernel<decltype(src)::value, T, decltype(nb)::value>), grid, block,
+                                       project_lds(nb, nmodes, sizeof(T)), st, int(rows), int(cols), xp, yp, int(nseg),
+                                       static_cast<const SegDesc*>(plan), mp, steps, int(nsteps), int(nmodes), bp, g + b0 * npts,
+                                       partial + b0 * nseg * nmodes, ld);
+                });
+            hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(ld)), block, 0, st, groups, ld, partial, static_cast<T*>(out));
+            return int(hipGetLastError());
+        });
+    });
 }
 
 }  // extern "C"

@@ -16,14 +16,10 @@
 // launch sums the partials of each output in a fixed order.  No atomics, so every run and every graph replay gives the same bits.
 #include "zernike_walk.h"
 
-#include "pm_entry.h"
-
 namespace pm {
 namespace {
 
-constexpr int kMaxProjectGroups = 1024;                 // workgroups of a projection (grid-stride beyond): the partial count per output
 constexpr int kDotIt = 2, kDotChunk = kThreads * kVec * kDotIt, kDotModes = 16;
-constexpr size_t kProjectLds = 64 * 1024;               // per-wave accumulators of a projection workgroup
 
 // ---------------------------------------------------------------- basis: K planes, write-bound
 template <typename T>
@@ -181,92 +177,16 @@ __global__ __launch_bounds__(kThreads) void modes_dot_kernel(int64_t npts, int n
     }
 }
 
-size_t elem_of(int32_t dtype) { return dtype == PM_F32 ? 4 : 8; }
-
-// 16-byte vectors: every plane of npts points starts on a 16-byte boundary, and so does every pointer given
-int vec_ok(int64_t npts, size_t elem, std::initializer_list<const void*> ptrs) {
-    if (npts % kVec) return 0;
-    for (const void* p : ptrs)
-        if (reinterpret_cast<uintptr_t>(p) % 16) return 0;
-    return 1;
-}
-
-int64_t tiles_of(int64_t npts) { return (npts + int64_t(kThreads) * kVec - 1) / (int64_t(kThreads) * kVec); }
-
-int64_t project_groups(int64_t npts) { return std::max<int64_t>(1, std::min<int64_t>(tiles_of(npts), kMaxProjectGroups)); }
-
 int64_t dot_chunks(int64_t npts) { return std::max<int64_t>(1, (npts + kDotChunk - 1) / kDotChunk); }
-
-// the largest of 8, 4, 2, 1 coefficient vectors per projection walk whose per-wave accumulators fit kProjectLds
-int project_nb(int32_t dtype, int64_t nmodes, int64_t batch) {
-    for (int nb = 8; nb > 1; nb >>= 1)
-        if (nb <= batch && size_t(kWaves) * nb * size_t(nmodes) * elem_of(dtype) <= kProjectLds) return nb;
-    return 1;
-}
 
 int check_walk(const char* who, int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
                int64_t nmodes) {
-    if (dtype != PM_F32 && dtype != PM_F64) return fail(PM_ERR_ARG, "%s: dtype must be PM_F32 or PM_F64", who);
+    if (!real_dtype(dtype)) return fail(PM_ERR_ARG, "%s: dtype must be PM_F32 or PM_F64", who);
     if (coords != PM_ZERNIKE_CARTESIAN && coords != PM_ZERNIKE_POLAR)
         return fail(PM_ERR_ARG, "%s: coords must be PM_ZERNIKE_CARTESIAN or PM_ZERNIKE_POLAR", who);
     if (!u || !v || !table || npts < 0 || nsteps < 0 || nmodes < 0 || nsteps > INT32_MAX || nmodes > INT32_MAX)
         return fail(PM_ERR_ARG, "%s: bad argument (null pointer or negative size)", who);
     return 0;
-}
-
-template <typename T>
-void launch_sum(int64_t npts, int polar, const void* u, const void* v, const void* table, int nsteps, int nmodes, int64_t batch,
-                const void* coefs, int accumulate, void* out, hipStream_t st) {
-    const dim3 grid{unsigned(tiles_of(npts))}, block{kThreads};
-    const int vec = vec_ok(npts, sizeof(T), {u, v, out});
-    for (int64_t b0 = 0; b0 < batch;) {
-        const int64_t left = batch - b0;
-        const T* c = (const T*)coefs + b0 * nmodes;
-        T* o = (T*)out + b0 * npts;
-#define PM_ZSUM(NB)                                                                                                                 \
-    hipLaunchKernelGGL((zernike_sum_kernel<T, NB>), grid, block, 0, st, npts, polar, (const T*)u, (const T*)v, (const ZStep<T>*)table, \
-                       nsteps, nmodes, c, accumulate, o, vec);                                                                           \
-    b0 += NB
-        if (left >= 8) { PM_ZSUM(8); }
-        else if (left >= 4) { PM_ZSUM(4); }
-        else if (left >= 2) { PM_ZSUM(2); }
-        else { PM_ZSUM(1); }
-#undef PM_ZSUM
-    }
-}
-
-template <typename T>
-void launch_project(int64_t npts, int polar, const void* u, const void* v, const void* table, int nsteps, int nmodes, int64_t batch,
-                    const void* g, void* out, void* ws, int nb, hipStream_t st) {
-    const int64_t groups = project_groups(npts);
-    const dim3 grid{unsigned(groups)}, block{kThreads};
-    T* partial = (T*)ws;
-    const int vec = vec_ok(npts, sizeof(T), {u, v, g});
-    for (int64_t b0 = 0; b0 < batch;) {
-        const int64_t left = batch - b0;
-        const T* gb = (const T*)g + b0 * npts;
-        T* pb = partial + b0 * nmodes;
-#define PM_ZPROJ(NB)                                                                                                                \
-    hipLaunchKernelGGL((zernike_project_kernel<T, NB>), grid, block, size_t(kWaves) * NB * nmodes * sizeof(T), st, npts, polar,      \
-                       (const T*)u, (const T*)v, (const ZStep<T>*)table, nsteps, nmodes, gb, pb, batch * nmodes, vec);                      \
-    b0 += NB
-        if (nb >= 8 && left >= 8) { PM_ZPROJ(8); }
-        else if (nb >= 4 && left >= 4) { PM_ZPROJ(4); }
-        else if (nb >= 2 && left >= 2) { PM_ZPROJ(2); }
-        else { PM_ZPROJ(1); }
-#undef PM_ZPROJ
-    }
-    hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(batch * nmodes)), block, 0, st, groups, batch * nmodes, (const T*)partial,
-                       (T*)out);
-}
-
-template <typename T>
-void launch_dot(int64_t nmodes, int64_t npts, const void* modes, int64_t mstride, const void* g, void* out, void* ws, hipStream_t st) {
-    const int64_t chunks = dot_chunks(npts);
-    const dim3 grid(unsigned(chunks), unsigned((nmodes + kDotModes - 1) / kDotModes)), block(kThreads);
-    const int vec = vec_ok(npts, sizeof(T), {modes, g}) && mstride % kVec == 0;
-    hipLaunchKernelGGL(modes_dot_kernel<T>, grid, block, 0, st, npts, int(nmodes), (const T*)modes, mstride, (const T*)g, (T*)ws, vec);
-    hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(nmodes)), block, 0, st, chunks, nmodes, (const T*)ws, (T*)out);
 }
 
 }  // namespace
@@ -282,17 +202,13 @@ int pm_zernike_basis(int32_t dtype, int32_t coords, int64_t npts, const void* u,
     if (!out) return fail(PM_ERR_ARG, "pm_zernike_basis: bad argument (null pointer)");
     if (tiles_of(npts) > INT32_MAX) return fail(PM_ERR_ARG, "pm_zernike_basis: %lld points is too many", (long long)npts);
     if (npts == 0 || nmodes == 0) return 0;
-    hipStream_t st = PM_STREAM(stream);
-    const int polar = coords == PM_ZERNIKE_POLAR;
-    const dim3 grid{unsigned(tiles_of(npts))}, block{kThreads};
-    const int vec = vec_ok(npts, elem_of(dtype), {u, v, out});
-    if (dtype == PM_F32)
-        hipLaunchKernelGGL(zernike_basis_kernel<float>, grid, block, 0, st, npts, polar, (const float*)u, (const float*)v,
-                           (const ZStep<float>*)table, int(nsteps), int(nmodes), (float*)out, vec);
-    else
-        hipLaunchKernelGGL(zernike_basis_kernel<double>, grid, block, 0, st, npts, polar, (const double*)u, (const double*)v,
-                           (const ZStep<double>*)table, int(nsteps), int(nmodes), (double*)out, vec);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_zernike_basis", [&](auto real) {
+        using T = decltype(real);
+        hipLaunchKernelGGL(zernike_basis_kernel<T>, dim3(unsigned(tiles_of(npts))), dim3(kThreads), 0, PM_STREAM(stream), npts,
+                           coords == PM_ZERNIKE_POLAR, static_cast<const T*>(u), static_cast<const T*>(v), static_cast<const ZStep<T>*>(table),
+                           int(nsteps), int(nmodes), static_cast<T*>(out), vec_ok(npts, {u, v, out}));
+        return int(hipGetLastError());
+    });
 }
 
 int pm_zernike_sum(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
@@ -301,17 +217,25 @@ int pm_zernike_sum(int32_t dtype, int32_t coords, int64_t npts, const void* u, c
     if (!out || !coefs || batch < 0) return fail(PM_ERR_ARG, "pm_zernike_sum: bad argument (null pointer or negative batch)");
     if (tiles_of(npts) > INT32_MAX) return fail(PM_ERR_ARG, "pm_zernike_sum: %lld points is too many", (long long)npts);
     if (npts == 0 || batch == 0) return 0;
-    hipStream_t st = PM_STREAM(stream);
-    const int polar = coords == PM_ZERNIKE_POLAR;
-    if (dtype == PM_F32)
-        launch_sum<float>(npts, polar, u, v, table, int(nsteps), int(nmodes), batch, coefs, accumulate != 0, out, st);
-    else
-        launch_sum<double>(npts, polar, u, v, table, int(nsteps), int(nmodes), batch, coefs, accumulate != 0, out, st);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_zernike_sum", [&](auto real) {
+        using T = decltype(real);
+        const T *up = static_cast<const T*>(u), *vp = static_cast<const T*>(v), *c = static_cast<const T*>(coefs);
+        const ZStep<T>* steps = static_cast<const ZStep<T>*>(table);
+        T* o = static_cast<T*>(out);
+        const dim3 grid{unsigned(tiles_of(npts))}, block{kThreads};
+        const int vec = vec_ok(npts, {u, v, out});
+        for (int64_t b0 = 0; b0 < batch;)
+            b0 += by_nb(batch - b0, 8, [&](auto nb) {
+                hipLaunchKernelGGL((zernike_sum_kernel<T, decltype(nb)::value>), grid, block, 0, PM_STREAM(stream), npts,
+                                   coords == PM_ZERNIKE_POLAR, up, vp, steps, int(nsteps), int(nmodes), c + b0 * nmodes, accumulate != 0,
+                                   o + b0 * npts, vec);
+            });
+        return int(hipGetLastError());
+    });
 }
 
 size_t pm_zernike_project_workspace(int32_t dtype, int64_t npts, int64_t nmodes, int64_t batch) {
-    if ((dtype != PM_F32 && dtype != PM_F64) || npts < 0 || nmodes < 0 || batch < 0) return 0;
+    if (!real_dtype(dtype) || npts < 0 || nmodes < 0 || batch < 0) return 0;
     return size_t(project_groups(npts)) * size_t(batch) * size_t(nmodes) * elem_of(dtype);
 }
 
@@ -320,31 +244,41 @@ int pm_zernike_project(int32_t dtype, int32_t coords, int64_t npts, const void* 
     if (int rc = check_walk("pm_zernike_project", dtype, coords, npts, u, v, table, nsteps, nmodes)) return rc;
     if (!out || !databar || batch < 0) return fail(PM_ERR_ARG, "pm_zernike_project: bad argument (null pointer or negative batch)");
     if (batch * nmodes > INT32_MAX) return fail(PM_ERR_ARG, "pm_zernike_project: batch * nmodes is too large");
-    if (size_t(kWaves) * size_t(nmodes) * elem_of(dtype) > kProjectLds)
+    if (project_lds(1, nmodes, elem_of(dtype)) > kProjectLds)
         return fail(PM_ERR_UNSUPPORTED, "pm_zernike_project: %lld modes do not fit the workgroup's accumulators", (long long)nmodes);
     if (batch == 0 || nmodes == 0) return 0;
     const size_t need = pm_zernike_project_workspace(dtype, npts, nmodes, batch);
     if (!workspace || workspace_bytes < need)
         return fail(PM_ERR_WORKSPACE, "pm_zernike_project: workspace of %zu bytes is smaller than the %zu pm_zernike_project_workspace asks for",
                     workspace_bytes, need);
-    hipStream_t st = PM_STREAM(stream);
-    const int polar = coords == PM_ZERNIKE_POLAR;
-    const int nb = project_nb(dtype, nmodes, batch);
-    if (dtype == PM_F32)
-        launch_project<float>(npts, polar, u, v, table, int(nsteps), int(nmodes), batch, databar, out, workspace, nb, st);
-    else
-        launch_project<double>(npts, polar, u, v, table, int(nsteps), int(nmodes), batch, databar, out, workspace, nb, st);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_zernike_project", [&](auto real) {
+        using T = decltype(real);
+        const T *up = static_cast<const T*>(u), *vp = static_cast<const T*>(v), *g = static_cast<const T*>(databar);
+        const ZStep<T>* steps = static_cast<const ZStep<T>*>(table);
+        T* partial = static_cast<T*>(workspace);
+        hipStream_t st = PM_STREAM(stream);
+        const int64_t groups = project_groups(npts), nout = batch * nmodes;
+        const dim3 grid{unsigned(groups)}, block{kThreads};
+        const int vec = vec_ok(npts, {u, v, databar});
+        for (int64_t b0 = 0; b0 < batch;)
+            b0 += by_nb(batch - b0, project_nb(dtype, nmodes, batch), [&](auto nb) {
+                hipLaunchKernelGGL((zernike_project_kernel<T, decltype(nb)::value>), grid, block, project_lds(nb, nmodes, sizeof(T)), st, npts,
+                                   coords == PM_ZERNIKE_POLAR, up, vp, steps, int(nsteps), int(nmodes), g + b0 * npts, partial + b0 * nmodes,
+                                   nout, vec);
+            });
+        hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(nout)), block, 0, st, groups, nout, partial, static_cast<T*>(out));
+        return int(hipGetLastError());
+    });
 }
 
 size_t pm_modes_dot_workspace(int32_t dtype, int64_t nmodes, int64_t npts) {
-    if ((dtype != PM_F32 && dtype != PM_F64) || nmodes < 0 || npts < 0) return 0;
+    if (!real_dtype(dtype) || nmodes < 0 || npts < 0) return 0;
     return size_t(dot_chunks(npts)) * size_t(nmodes) * elem_of(dtype);
 }
 
 int pm_modes_dot(int32_t dtype, int64_t nmodes, int64_t npts, const void* modes, int64_t mode_stride, const void* v, void* out, void* workspace,
                  size_t workspace_bytes, void* stream) {
-    if (dtype != PM_F32 && dtype != PM_F64) return fail(PM_ERR_ARG, "pm_modes_dot: dtype must be PM_F32 or PM_F64");
+    if (!real_dtype(dtype)) return fail(PM_ERR_ARG, "pm_modes_dot: dtype must be PM_F32 or PM_F64");
     if (!modes || !v || !out || nmodes < 0 || npts < 0 || (nmodes > 1 && mode_stride < npts) || nmodes > 65535 * int64_t(kDotModes) ||
         dot_chunks(npts) > INT32_MAX)
         return fail(PM_ERR_ARG, "pm_modes_dot: bad argument (null pointer, negative size or mode_stride < npts)");
@@ -353,12 +287,18 @@ int pm_modes_dot(int32_t dtype, int64_t nmodes, int64_t npts, const void* modes,
     if (!workspace || workspace_bytes < need)
         return fail(PM_ERR_WORKSPACE, "pm_modes_dot: workspace of %zu bytes is smaller than the %zu pm_modes_dot_workspace asks for",
                     workspace_bytes, need);
-    hipStream_t st = PM_STREAM(stream);
-    if (dtype == PM_F32)
-        launch_dot<float>(nmodes, npts, modes, mode_stride, v, out, workspace, st);
-    else
-        launch_dot<double>(nmodes, npts, modes, mode_stride, v, out, workspace, st);
-    return int(hipGetLastError());
+    return by_rdtype(dtype, "pm_modes_dot", [&](auto real) {
+        using T = decltype(real);
+        hipStream_t st = PM_STREAM(stream);
+        T* partial = static_cast<T*>(workspace);
+        const int64_t chunks = dot_chunks(npts);
+        const dim3 grid(unsigned(chunks), unsigned((nmodes + kDotModes - 1) / kDotModes)), block(kThreads);
+        const int vec = vec_ok(npts, {modes, v}) && mode_stride % kVec == 0;
+        hipLaunchKernelGGL(modes_dot_kernel<T>, grid, block, 0, st, npts, int(nmodes), static_cast<const T*>(modes), mode_stride,
+                           static_cast<const T*>(v), partial, vec);
+        hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(nmodes)), block, 0, st, chunks, nmodes, partial, static_cast<T*>(out));
+        return int(hipGetLastError());
+    });
 }
 
 }  // extern "C"

@@ -1,8 +1,11 @@
 // The Zernike table walk shared by csrc/zernike.hip and csrc/segmented.hip (gfx950): the step layout, the wave tile of points, its
 // 16-byte loads and stores, the walk itself and the fixed-order second stage of the deterministic reductions.  See zernike.hip for
-// the table and prysm_amd/polynomials/zernike_plan.py for how it is built.
+// the table and prysm_amd/polynomials/zernike_plan.py for how it is built.  csrc/qpoly.hip walks a table of its own over the same tile.
+// At the end: what the host halves of the three units need to launch over that tile (grids, the 16-byte test, the projection's LDS).
 #pragma once
-#include "pm_internal.h"
+#include <initializer_list>
+
+#include "pm_entry.h"
 
 namespace pm {
 namespace {
@@ -170,6 +173,32 @@ __global__ __launch_bounds__(kThreads) void reduce_partials_kernel(int64_t ngrou
         for (int w = 1; w < kWaves; ++w) t += sw[w];
         out[o] = t;
     }
+}
+
+// ---------------------------------------------------------------- host: launching over the wave tile
+constexpr int kMaxProjectGroups = 1024;                 // workgroups of a projection (grid-stride beyond): the partial count per output
+constexpr size_t kProjectLds = 64 * 1024;               // per-wave accumulators of a projection workgroup
+
+// 16-byte vectors: every plane of npts points starts on a 16-byte boundary, and so does every pointer given (null: not read)
+int vec_ok(int64_t npts, std::initializer_list<const void*> ptrs) {
+    if (npts % kVec) return 0;
+    for (const void* p : ptrs)
+        if (!aligned(p, 16)) return 0;
+    return 1;
+}
+
+int64_t tiles_of(int64_t npts) { return (npts + int64_t(kThreads) * kVec - 1) / (int64_t(kThreads) * kVec); }
+
+int64_t project_groups(int64_t npts, int64_t most = kMaxProjectGroups) { return std::max<int64_t>(1, std::min(tiles_of(npts), most)); }
+
+// the LDS of a projection workgroup: an accumulator per (wave, coefficient vector, mode)
+size_t project_lds(int64_t nb, int64_t nmodes, size_t elem) { return size_t(kWaves) * size_t(nb) * size_t(nmodes) * elem; }
+
+// the largest of 8, 4, 2, 1 coefficient vectors per projection walk whose per-wave accumulators fit kProjectLds
+int project_nb(int32_t dtype, int64_t nmodes, int64_t batch) {
+    for (int nb = 8; nb > 1; nb >>= 1)
+        if (nb <= batch && project_lds(nb, nmodes, elem_of(dtype)) <= kProjectLds) return nb;
+    return 1;
 }
 
 }  // namespace

@@ -156,6 +156,37 @@ def test_stacks_equal_single_calls(dt):
         assert _rel(Ac[b], tonp(P.Qcon_sum_adjoint(Gc[b], range(9), u))) < tol
 
 
+def _stack_of_15(dt, npts, nms):
+    from prysm_amd import polynomials as P
+    rng = np.random.default_rng(15)
+    x, y = (rng.uniform(-0.7, 0.7, npts).astype(dt) for _ in range(2))
+    C = rng.standard_normal((15, len(nms))).astype(dt)
+    S = tonp(P.Q2d_sum(C, nms, x, y))
+    assert S.shape == (15, npts) and S.dtype == dt
+    tol = 1e-14 if dt == np.float64 else 1e-6
+    for b in range(15):
+        assert _rel(S[b], tonp(P.Q2d_sum(C[b], nms, x, y))) < tol
+    G = rng.standard_normal((15, npts)).astype(dt)
+    A = tonp(P.Q2d_sum_adjoint(G, nms, x, y))
+    assert A.shape == (15, len(nms)) and A.dtype == dt
+    for b in range(15):
+        assert _rel(A[b], tonp(P.Q2d_sum_adjoint(G[b], nms, x, y))) < tol
+
+
+@pytest.mark.parametrize('dt', [np.float64, np.float32])
+@pytest.mark.parametrize('npts', [1024, 1027])
+def test_a_stack_of_15_equals_single_calls(dt, npts):
+    """15 = 8 + 4 + 2 + 1 vectors per walk, each piece at its own offset into the coefficients, the output and the partials; 1024 points
+    take the 16-byte path, 1027 the element-wise one"""
+    _stack_of_15(dt, npts, [(n, m) for n in range(2) for m in range(-2, 3)])
+
+
+def test_a_stack_of_15_with_two_vectors_per_projection_walk():
+    """625 modes in fp64: the accumulators of a projection workgroup (64 KiB) hold two vectors of them, not four, so the 15 go as seven
+    pairs and a single one"""
+    _stack_of_15(np.float64, 1027, [(n, m) for n in range(25) for m in range(-12, 13)])
+
+
 def test_odd_point_counts_and_views():
     """point counts that are not a multiple of 4 and coordinates that start off a 16-byte boundary take the element-wise path"""
     from prysm_amd import polynomials as P

@@ -149,6 +149,41 @@ def test_stacks_equal_single_calls_and_adjoint_is_bitwise_reproducible(fx, i):
             assert torch.allclose(a[b], ap.compose_opd_adjoint(g[b]), rtol=1e-13, atol=1e-13)
 
 
+def _stack_of_15(dt, rows, cols, nms):
+    from prysm_amd import segmented as SG
+    from prysm_amd.polynomials import zernike_nm_seq
+    x, y = np.meshgrid(np.linspace(-2.1, 2.1, cols), np.linspace(-2.1, 2.1, rows))
+    ap = SG.CompositeHexagonalAperture(x.astype(dt), y.astype(dt), 1, 1.32, 0.05, segment_angle=90)
+    ap.prepare_opd_bases(zernike_nm_seq, nms)
+    S, K = len(ap.windows), len(nms)
+    rng = np.random.default_rng(15)
+    c = torch.from_numpy(rng.standard_normal((15, S, K)).astype(dt)).cuda()
+    st = ap.compose_opd(c)
+    assert st.shape == (15, rows, cols) and tonp(st).dtype == dt
+    for b in range(15):
+        assert torch.equal(st[b], ap.compose_opd(c[b]))
+    g = torch.from_numpy(rng.standard_normal((15, rows, cols)).astype(dt)).cuda()
+    a = ap.compose_opd_adjoint(g).clone()
+    assert a.shape == (15, S, K)
+    tol = 1e-13 if dt == np.float64 else 1e-5
+    for b in range(15):
+        assert torch.allclose(a[b], ap.compose_opd_adjoint(g[b]), rtol=tol, atol=tol)
+
+
+@pytest.mark.parametrize('dt', [np.float64, np.float32])
+@pytest.mark.parametrize('shape', [(64, 64), (63, 65)])
+def test_a_stack_of_15_equals_single_calls(dt, shape):
+    """15 = 8 + 4 + 2 + 1 coefficient stacks per walk, each piece at its own offset into the coefficients, the output and the partials;
+    64 x 64 points take the 16-byte path, 63 x 65 = 4095 the element-wise one"""
+    _stack_of_15(dt, *shape, [(n, m) for n in range(4) for m in range(-n, n + 1, 2)])
+
+
+def test_a_stack_of_15_with_two_stacks_per_projection_walk():
+    """630 modes in fp64: the accumulators of a projection workgroup (64 KiB) hold two stacks' worth of them, not four, so the 15 go as
+    seven pairs and a single one"""
+    _stack_of_15(np.float64, 63, 65, [(n, m) for n in range(35) for m in range(-n, n + 1, 2)])
+
+
 def test_graph_replay_reads_coefficients_on_the_device(fx):
     from prysm_amd import graph
     ap, x = prepared(fx, 1)
