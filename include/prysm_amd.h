@@ -536,6 +536,58 @@ int pm_bayer_class_max(int32_t dtype, int32_t classes, int64_t batch, int64_t m,
 int pm_bayer_scale(int32_t dtype, int32_t classes, int32_t cfa, int64_t batch, int64_t m, int64_t n, void* data, int64_t ld, int64_t bstride,
                    const double* gains, int32_t safe, const double* saturation, const void* maxima, void* stream);
 
+/* Gradient-based optimisation (csrc/optym.hip): prysm/x/optym.  REAL data, PM_F32 or PM_F64; arrays of any shape are taken flat and
+ * contiguous.  Nothing here reads a device value on the host, so an iteration (model, cost, adjoints, step) can be captured in a graph.
+ * prysm_amd/x/optym_plan.py is the same arithmetic in numpy. */
+enum { PM_COST_MSE = 0, PM_COST_BGI = 1, PM_COST_NLL = 2 };
+enum { PM_OPT_GD = 0, PM_OPT_ADAGRAD = 1, PM_OPT_RMSPROP = 2, PM_OPT_ADAM = 3, PM_OPT_RADAM = 4, PM_OPT_ADAMOMENTUM = 5, PM_OPT_YOGI = 6 };
+enum { PM_ACT_TANH = 0, PM_ACT_ARCTAN = 1, PM_ACT_SOFTPLUS = 2, PM_ACT_SIGMOID = 3 };
+enum { PM_GRAD_FORWARD_X = 0, PM_GRAD_ADJOINT_X = 1, PM_GRAD_FORWARD_Y = 2, PM_GRAD_ADJOINT_Y = 3 };
+
+/* mean_square_error (x/optym/cost.py:73-96), bias_and_gain_invariant_error (cost.py:30-70) and negative_loglikelihood (cost.py:99-125)
+ * with the mask handling of cost.py:8-27: the cost to `cost`, a DEVICE cell of dtype, and d cost / d M to grad (n values of dtype, zero
+ * where the mask is false).  M, D: n values; D may be NULL for PM_COST_NLL, whose target is then d_scalar.  mask: n bytes (nonzero
+ * keeps the element) or NULL.  The mask is a predicate, nothing is compacted: the selected count N is one of the sums.  Every sum is
+ * accumulated in double, per workgroup and then by one workgroup in a fixed order (no atomics: the result is the same bits run after
+ * run), and 1/N, alpha, beta and R are formed in double on the device.  PM_COST_MSE and PM_COST_NLL are three launches, PM_COST_BGI
+ * four (its second pass carries sum(raw_err^2), so the cost is the reference's sum of squared residuals).  An all-false mask gives a
+ * NaN cost and a zero gradient.  workspace: pm_optym_cost_workspace() DEVICE bytes, 8-byte aligned. */
+size_t pm_optym_cost_workspace(void);
+int pm_optym_cost(int32_t dtype, int32_t kind, int64_t n, const void* M, const void* D, double d_scalar, const void* mask, void* cost, void* grad,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* One step of GradientDescent, AdaGrad, RMSProp, Adam, RAdam, AdaMomentum or Yogi (x/optym/optimizers.py:205-500) as two launches.
+ * pm_optym_advance (one thread): counter (a DEVICE int64, the reference's self.iter) += 1 = k, and coef (eight DEVICE doubles) =
+ * 1 - beta1^k, 1 - beta2^k, RAdam's rho and r (optimizers.py:405-413), its branch (1 where rho >= 5), sqrt(1 - beta2^k), 0, 0.
+ * pm_optym_step (one kernel over the n variables): the projected gradient (_project_gradient, optimizers.py:85-96), the moment update,
+ * the step and the clamp (_project_bounds, optimizers.py:79-82), in dtype, each expression as the reference writes it.  x, s1 (m, or
+ * the accumulator of AdaGrad / RMSProp; NULL for PM_OPT_GD) and s2 (v; from PM_OPT_ADAM on) are updated IN PLACE; the pre-step
+ * iterate goes to x_prev.  beta1 is RMSProp's gamma.  lower / upper: n values each (infinite where a side is free) or both NULL; with
+ * bounds the kernel also stores g_step (n values) and active (n bytes: the post-step iterate sits on a finite bound,
+ * _store_bounded_step_metadata, optimizers.py:99-112).  coef is read from PM_OPT_ADAM on. */
+int pm_optym_advance(int32_t kind, double beta1, double beta2, void* counter, void* coef, void* stream);
+int pm_optym_step(int32_t dtype, int32_t kind, int64_t n, void* x, const void* g, void* s1, void* s2, const void* lower, const void* upper,
+                  double alpha, double beta1, double beta2, double eps, const void* coef, void* x_prev, void* g_step, void* active, void* stream);
+
+/* forward (backprop == 0) or backprop of Tanh, Arctan, Softplus and Sigmoid (x/optym/activation.py:207-252) with the affine parameters
+ * a, x0, y0: one sweep, out may be x. */
+int pm_optym_activation(int32_t dtype, int32_t kind, int32_t backprop, int64_t n, const void* x, double a, double x0, double y0, void* out,
+                        void* stream);
+
+/* Softmax.forward (activation.py:27-52) over rows x K, K last and contiguous: out = exp(x - max) / sum.  A row takes the smallest
+ * power-of-two group of lanes that holds K, at most 64, and longer rows loop.  With u (rows x K uniform variates) the logits are
+ * (x - log(-log(u + eps) + eps)) / tau, GumbelSoftmax.forward (activation.py:104-121), formed in the load, once per element (rows
+ * longer than 64 stage their logits in out).
+ * pm_optym_softmax_backprop (activation.py:54-83, 123-127): gin_k = y_k (grad_k S - sum_j grad_j y_j) / tau from the forward result y,
+ * with S = sum_j y_j (1 up to the rounding of y), the two sums and the bracket in double: the reference's grad_k - sum_j grad_j y_j
+ * cancels down to the rounding of y on a saturated row. */
+int pm_optym_softmax(int32_t dtype, int64_t rows, int64_t K, const void* x, const void* u, double tau, double eps, void* out, void* stream);
+int pm_optym_softmax_backprop(int32_t dtype, int64_t rows, int64_t K, const void* y, const void* grad, double tau, void* gin, void* stream);
+
+/* SpatialGradient2D (x/optym/operators.py:5-48) on a contiguous m x n array: forward differences over the interior of an axis and
+ * their adjoints, the adjoints as gathers.  in and out must differ. */
+int pm_optym_spatial_gradient(int32_t dtype, int32_t op, int64_t m, int64_t n, const void* in, void* out, void* stream);
+
 /* Segmented apertures (csrc/segmented.hip): CompositeHexagonalAperture.compose_opd (prysm/segmented.py:178-285) and its adjoint.
  * The grid is rows x cols REAL points (dtype PM_F32 / PM_F64, computed in that precision); x, y are the aperture's DEVICE coordinate
  * arrays.  `plan` is a DEVICE array of nseg 80-byte segment records built by prysm_amd/segmented.py (struct pm::SegDesc: int32 y0, x0,
