@@ -410,6 +410,66 @@ size_t pm_qpoly_project_workspace(int32_t dtype, int64_t npts, int64_t nmodes, i
 int pm_qpoly_project(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
                      int64_t nmodes, int64_t batch, const void* databar, void* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Polynomial families defined by a three-term recurrence, without a stored basis (csrc/recur.hip): Jacobi, Chebyshev of the four
+ * kinds, Legendre, Hermite He / H, Laguerre, Dickson of both kinds and the XY monomials (prysm/polynomials/jacobi.py, cheby.py,
+ * legendre.py, hermite.py, laguerre.py, dickson.py, xy.py).  `table` is a DEVICE array of nsteps = nmax + 1 records built by
+ * prysm_amd/polynomials/recur_plan.py (struct pm::RStep: T a, b, c; int32 slot -- 16 bytes for PM_F32, 32 with padding for PM_F64).
+ * Record k is order k: P_k = (a + b x) P_{k-1} - c P_{k-2} and, for the derivative, D_k = b P_{k-1} + (a + b x) D_{k-1} - c D_{k-2},
+ * walked from P_{-1} = 1, P_{-2} = 0, D = 0, so record 0 is (P_0, 0, 0) and record 1 has c = 0; slot is the output plane (or the
+ * coefficient) of order k, a slot outside [0, nout) writes nothing.  REAL dtypes PM_F32 / PM_F64, computed in that precision.
+ * The argument of the walk: PM_RECUR_X, u[p] (v is not read and may be NULL); PM_RECUR_R2, 2 (u^2 + v^2) / radius^2 - 1 from the
+ * Cartesian arrays u = x, v = y (jacobi.py:376-413). */
+enum { PM_RECUR_X = 0, PM_RECUR_R2 = 1 };
+
+/* out (nout, npts) = P_k and / or out_der (nout, npts) = dP_k / d(argument), either may be NULL, one launch: the *_seq and *_der_seq
+ * of cheby.py:74-321, legendre.py:34-110, hermite.py:84-120, laguerre.py:65-140, dickson.py:87-275, jacobi.py:148-276 (jacobi_seq,
+ * jacobi_der_seq, jacobi_seq_with_der) and their single-order forms. */
+int pm_recur_basis(int32_t dtype, int32_t form, int64_t npts, const void* u, const void* v, double radius, const void* table, int64_t nsteps,
+                   int64_t nout, void* out, void* out_der, void* stream);
+
+/* out[b][p] (+)= sum_k coefs[b][slot_k] P_k for batch coefficient vectors (coefs: DEVICE, batch x ncoef, read at launch time), up to 8
+ * vectors per walk; any of the three outputs may be NULL.  PM_RECUR_X: out_dx = sum_k c D_k, out_dy must be NULL.  PM_RECUR_R2:
+ * out_dx = dz/du 4 x / R^2, out_dy = dz/du 4 y / R^2.  jacobi_sum_clenshaw with dense orders (jacobi.py:279-316), jacobi_radial_sum
+ * (376-389), jacobi_radial_sum_der_xy (392-413) without the basis. */
+int pm_recur_sum(int32_t dtype, int32_t form, int64_t npts, const void* u, const void* v, double radius, const void* table, int64_t nsteps,
+                 int64_t ncoef, int64_t batch, const void* coefs, int32_t accumulate, void* out, void* out_dx, void* out_dy, void* stream);
+
+/* out[b][k] = sum_p databar[b][p] P_k(u_p), the adjoint of pm_recur_sum with respect to the coefficients (the reference has none).
+ * der != 0: the derivative basis, for PM_RECUR_R2 with the chain factors: sum_p (databar 4 x / R^2 + databar2 4 y / R^2) D_k, databar
+ * the adjoint of out_dx and databar2 (may be NULL) of out_dy; accumulate != 0 adds into out.  Two launches as pm_zernike_project: per-workgroup partials in a fixed
+ * order into the workspace (pm_recur_project_workspace bytes), then a fixed-order sum -- no atomics, bitwise reproducible. */
+size_t pm_recur_project_workspace(int32_t dtype, int64_t npts, int64_t nout, int64_t batch);
+int pm_recur_project(int32_t dtype, int32_t form, int64_t npts, const void* u, const void* v, double radius, const void* table, int64_t nsteps,
+                     int64_t nout, int64_t batch, int32_t der, const void* databar, const void* databar2, int32_t accumulate, void* out,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* The separable sum on a rows x cols Cartesian grid: z[b][i][j] = sum_{n,m} coefs[b][n][m] Py_n(y[i]) Px_m(x[j]) with
+ * zx = inv_xnorm dz/dx and zy = inv_ynorm dz/dy, the outputs chosen by the mask `what`; x[cols], y[rows], one table per axis (nx,
+ * ny records, slot unused) and the dense DEVICE matrices coefs (batch, ny, nx), read at launch time.  One launch, factored through
+ * t[n][j] = sum_m C[n][m] Px_m(x_j) in LDS; every output is stored once and no basis is stored.  Output rows lie ld elements apart,
+ * members of the stack bstride.  An axis takes at most 64 orders (PM_ERR_UNSUPPORTED beyond).  cheby1_2d_sum[_der_xy]
+ * (cheby.py:324-362, x_norm = 1 / inv_xnorm) and xy_sum[_der_xy] (xy.py:334-383, three matrix products over stored power tables). */
+enum { PM_RECUR2_Z = 1, PM_RECUR2_ZX = 2, PM_RECUR2_ZY = 4 };
+int pm_recur2_sum(int32_t dtype, int64_t rows, int64_t cols, const void* x, const void* y, const void* xtable, int64_t nx, const void* ytable,
+                  int64_t ny, int64_t batch, const void* coefs, int32_t what, double inv_xnorm, double inv_ynorm, void* z, void* zx, void* zy,
+                  int64_t ld, int64_t bstride, void* stream);
+
+/* out[b][n][m] (+)= sum_{i,j} databar[b][i][j] Fy_n(y[i]) Fx_m(x[j]): the adjoint of ONE of the maps of pm_recur2_sum with respect to
+ * coefs (the reference has none) -- what = PM_RECUR2_Z (F the values), PM_RECUR2_ZX (Fx the derivative, times inv_xnorm) or
+ * PM_RECUR2_ZY (Fy the derivative, times inv_ynorm); accumulate != 0 adds into out, so the three adjoints can share one.  Two
+ * launches: the rows of each chunk reduced per column into the workspace (pm_recur2_project_workspace bytes), then the chunks summed
+ * in order and the columns contracted in a fixed order -- no atomics, bitwise reproducible. */
+size_t pm_recur2_project_workspace(int32_t dtype, int64_t rows, int64_t cols, int64_t ny, int64_t batch);
+int pm_recur2_project(int32_t dtype, int64_t rows, int64_t cols, const void* x, const void* y, const void* xtable, int64_t nx,
+                      const void* ytable, int64_t ny, int64_t batch, int32_t what, double inv_xnorm, double inv_ynorm, const void* databar,
+                      int64_t ld, int64_t bstride, int32_t accumulate, void* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* out[k][i][j] = ty[n_k][i] tx[m_k][j] for the nk DEVICE int32 pairs (m_k, n_k) of `pairs`, from two stored 1-D tables ty (nty, rows)
+ * and tx (ntx, cols) (two small pm_recur_basis calls); a pair outside the tables writes nothing.  xy_seq, xy_der_x_seq, xy_der_y_seq,
+ * xy_der_xy_seq (xy.py:166-300). */
+int pm_recur2_outer(int32_t dtype, int64_t rows, int64_t cols, int64_t nk, const void* ty, int64_t nty, const void* tx, int64_t ntx,
+                    const void* pairs, void* out, void* stream);
+
 /* Coordinates (csrc/geometry.hip): REAL arrays of dtype PM_F32 / PM_F64, computed in that precision. */
 
 /* make_xy_grid (prysm/coordinates.py:344-378) with fftrange (fttools.py:13-15): element j of an axis of n samples is (j - n / 2)

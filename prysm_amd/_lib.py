@@ -26,6 +26,8 @@ PM_ERR_ARG, PM_ERR_UNSUPPORTED, PM_ERR_WORKSPACE = -1, -2, -3
 PM_LATTICE_SCATTER, PM_LATTICE_GATHER = 0, 1
 PM_ZERNIKE_CARTESIAN, PM_ZERNIKE_POLAR = 0, 1
 PM_QPOLY_RADIAL = 2
+PM_RECUR_X, PM_RECUR_R2 = 0, 1
+PM_RECUR2_Z, PM_RECUR2_ZX, PM_RECUR2_ZY = 1, 2, 4
 PM_SEGMENT_ZERNIKE, PM_SEGMENT_STORED = 0, 1
 PM_COORDS_GRID, PM_COORDS_SEPARABLE, PM_COORDS_POINTWISE = 0, 1, 2
 PM_SDF_MASK, PM_SDF_DISTANCE, PM_SDF_COVERAGE = 0, 1, 2
@@ -117,6 +119,17 @@ SIGNATURES = {
     'pm_qpoly_sum': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp]),
     'pm_qpoly_project_workspace': (c_sz, [c_i32, c_i64, c_i64, c_i64]),
     'pm_qpoly_project': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'pm_recur_basis': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_vp, c_f64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    'pm_recur_sum': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_vp, c_f64, c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'pm_recur_project_workspace': (c_sz, [c_i32, c_i64, c_i64, c_i64]),
+    'pm_recur_project': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_vp, c_f64, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_sz,
+                                 c_vp]),
+    'pm_recur2_sum': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i32, c_f64, c_f64, c_vp, c_vp, c_vp,
+                              c_i64, c_i64, c_vp]),
+    'pm_recur2_project_workspace': (c_sz, [c_i32, c_i64, c_i64, c_i64, c_i64]),
+    'pm_recur2_project': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_f64, c_f64, c_vp, c_i64, c_i64,
+                                  c_i32, c_vp, c_vp, c_sz, c_vp]),
+    'pm_recur2_outer': (c_i32, [c_i32, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
     'pm_xy_grid': (c_i32, [c_i32, c_i64, c_i64, c_f64, c_i32, c_vp, c_vp, c_vp]),
     'pm_cart_to_polar': (c_i32, [c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'pm_polar_to_cart': (c_i32, [c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
