@@ -648,6 +648,40 @@ int pm_optym_softmax_backprop(int32_t dtype, int64_t rows, int64_t K, const void
  * their adjoints, the adjoints as gathers.  in and out must differ. */
 int pm_optym_spatial_gradient(int32_t dtype, int32_t op, int64_t m, int64_t n, const void* in, void* out, void* stream);
 
+/* Thin-film multilayers (csrc/thinfilm.hip): prysm/thinfilm.py and the core of prysm/x/coatings (stack.py, diff.py).  One thread per
+ * sample k < K walks the L layers (ambient side first) in registers.  dtype PM_C64 or PM_C128; real operands are of the matching real
+ * type.  Operands, all DEVICE arrays: wvl (wavelength) and theta (the ambient angle, RADIANS), real; n0 (ambient index) and nsub
+ * (substrate index), complex; the layer tables n (complex) and d (real, the unit of wvl).  Every operand has a sample stride `_ss` of
+ * 0 (one value shared by all samples) or 1 (one per sample); layer j of a table starts `_ls` elements after layer j - 1 (at least K
+ * where the table is per sample).  prysm_amd/thinfilm_plan.py is the same arithmetic in numpy. */
+enum { PM_TF_S = 0, PM_TF_P = 1, PM_TF_BOTH = 2 };
+enum { PM_TF_T_STACK = 0, PM_TF_T_THINFILM = 1 };
+
+/* The characteristic-matrix sweep (x/coatings/stack.py:102-129, 174-203 and thinfilm.py:213-316): v = [1, eta_sub], v <- M_j v for
+ * j = L - 1 .. 0 with cos(theta_j) by _cos_snell (thinfilm.py:75-80), then r = (eta0 B - C) / (eta0 B + C), t = 2 eta0 / (eta0 B + C)
+ * from [B, C] = v.  pol selects s, p or both; with PM_TF_BOTH one sweep carries both vectors and every output has a leading axis of 2
+ * (s, then p).  r, t: K complex values per polarisation, required.  Optional outputs, NULL when not wanted: R = |r|^2 and
+ * T = Re eta_sub / Re eta0 |t|^2 (K reals; stack.py:304-334), the tangential fields E, H at the L + 1 boundaries ((L + 1) x K complex,
+ * boundary-major, together or not at all; stack.py:229-249) and the per-layer absorptance A (L x K reals).  t_convention
+ * PM_TF_T_THINFILM stores multilayer_stack_rt's t, which for p is t cos(theta_0) / cos(theta_sub) (from A00, thinfilm.py:297-311);
+ * T, E, H and A are always the stack's.  One launch.  K = 0 returns 0 without a launch; L = 0 is the bare interface. */
+int pm_tf_stack(int32_t dtype, int32_t pol, int32_t t_convention, int64_t K, int64_t L, const void* wvl, int64_t wvl_ss, const void* theta,
+                int64_t theta_ss, const void* n, int64_t n_ls, int64_t n_ss, const void* d, int64_t d_ls, int64_t d_ss, const void* nsub, int64_t nsub_ss,
+                const void* n0, int64_t n0_ss, void* r, void* t, void* R, void* T, void* E, void* H, void* A, void* stream);
+
+/* thickness_gradient (x/coatings/diff.py:162-201, 233-308) for R / T seeds: grad[j] = sum_k dF/dd_j, L reals, from dR and dT (K reals
+ * per polarisation, either may be NULL; with PM_TF_BOTH the seeds of p start seed_pstride elements after those of s, 0 = the same
+ * seeds).  The cotangent of M_j is a_j b_{j+1}^H -- b the unnormalised boundary vectors of the sweep from the substrate (kept in the
+ * workspace), a_0 = [Bbar, Cbar]^T, a_{j+1} = M_j^H a_j -- so no prefix or suffix product is stored and no matrix inverted.  The sum
+ * over samples is in double: one partial per wavefront and layer, then one workgroup per layer adds them in a fixed order (no atomics,
+ * the same bits run after run).  accumulate != 0 adds to grad.  Two launches.  K = 0 or L = 0 returns 0 without a launch.  workspace:
+ * pm_tf_thickness_grad_workspace bytes (0 for a dtype or pol it does not know), DEVICE, 16-byte aligned. */
+size_t pm_tf_thickness_grad_workspace(int32_t dtype, int32_t pol, int64_t K, int64_t L);
+int pm_tf_thickness_grad(int32_t dtype, int32_t pol, int64_t K, int64_t L, const void* wvl, int64_t wvl_ss, const void* theta, int64_t theta_ss,
+                         const void* n, int64_t n_ls, int64_t n_ss, const void* d, int64_t d_ls, int64_t d_ss, const void* nsub, int64_t nsub_ss,
+                         const void* n0, int64_t n0_ss, const void* dR, const void* dT, int64_t seed_pstride, int32_t accumulate, void* grad,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Segmented apertures (csrc/segmented.hip): CompositeHexagonalAperture.compose_opd (prysm/segmented.py:178-285) and its adjoint.
  * The grid is rows x cols REAL points (dtype PM_F32 / PM_F64, computed in that precision); x, y are the aperture's DEVICE coordinate
  * arrays.  `plan` is a DEVICE array of nseg 80-byte segment records built by prysm_amd/segmented.py (struct pm::SegDesc: int32 y0, x0,

@@ -39,6 +39,8 @@ PM_COST_MSE, PM_COST_BGI, PM_COST_NLL = 0, 1, 2
 PM_OPT_GD, PM_OPT_ADAGRAD, PM_OPT_RMSPROP, PM_OPT_ADAM, PM_OPT_RADAM, PM_OPT_ADAMOMENTUM, PM_OPT_YOGI = 0, 1, 2, 3, 4, 5, 6
 PM_ACT_TANH, PM_ACT_ARCTAN, PM_ACT_SOFTPLUS, PM_ACT_SIGMOID = 0, 1, 2, 3
 PM_GRAD_FORWARD_X, PM_GRAD_ADJOINT_X, PM_GRAD_FORWARD_Y, PM_GRAD_ADJOINT_Y = 0, 1, 2, 3
+PM_TF_S, PM_TF_P, PM_TF_BOTH = 0, 1, 2
+PM_TF_T_STACK, PM_TF_T_THINFILM = 0, 1
 
 c_i32, c_i64, c_f64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
 
@@ -158,6 +160,11 @@ SIGNATURES = {
     'pm_optym_softmax': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_vp, c_f64, c_f64, c_vp, c_vp]),
     'pm_optym_softmax_backprop': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_vp, c_f64, c_vp, c_vp]),
     'pm_optym_spatial_gradient': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    'pm_tf_stack': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
+                    c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'pm_tf_thickness_grad_workspace': (c_sz, [c_i32, c_i32, c_i64, c_i64]),
+    'pm_tf_thickness_grad': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
+                             c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_sz, c_vp]),
     'pm_segment_plan_check': (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64]),
     'pm_segment_compose': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                    c_vp, c_i32, c_vp, c_vp]),

@@ -785,6 +785,126 @@ def cgemm_abs2(A, B, opA=0, opB=0, alpha=1.0, out=None, weight=1.0):
     return out
 
 
+# --------------------------------------------------------------------------- thin films (csrc/thinfilm.hip)
+
+class TfOperands:
+    """The operands of the thin-film kernels for K flat samples, on the device: wvl and theta (radians) real, n0 and nsub complex,
+    each of K values or of one (shared by all samples); the layer tables n (complex) and d (real), (L, K) or (L, 1).  `d` is used
+    where it lies when it already is a contiguous device tensor of the real type (an optimizer's x at a fixed address)."""
+    __slots__ = ('cdtype', 'rdtype', 'K', 'L', 'wvl', 'theta', 'n', 'd', 'nsub', 'n0')
+
+    def __init__(self, cdtype, K, wvl, theta, n, d, nsub, n0):
+        if cdtype not in (torch.complex64, torch.complex128):
+            raise TypeError(f'thin films compute in complex64 or complex128, got {cdtype}')
+        self.cdtype, self.rdtype, self.K = cdtype, L._REAL_OF[cdtype], int(K)
+        self.wvl, self.theta = self._vector(wvl, self.rdtype, 'wavelength'), self._vector(theta, self.rdtype, 'angle')
+        self.nsub, self.n0 = self._vector(nsub, cdtype, 'substrate index'), self._vector(n0, cdtype, 'ambient index')
+        self.n = self._table(n, cdtype, 'indices')
+        self.L = self.n.shape[0]
+        self.d = None
+        self.set_thicknesses(d)
+
+    def _vector(self, v, dtype, what):
+        t = L.as_device(v, dtype).reshape(-1)
+        if t.numel() not in (1, self.K):
+            raise ValueError(f'{what}: {t.numel()} values for {self.K} samples')
+        return t
+
+    def _table(self, v, dtype, what):
+        t = L.as_device(v, dtype)
+        if t.numel() == 0:      # no layers: a bare interface
+            return torch.empty((0, 1), dtype=dtype, device=t.device)
+        t = t.reshape(t.shape[0], -1) if t.dim() >= 1 else t.reshape(1, 1)
+        if t.shape[1] not in (1, self.K):
+            raise ValueError(f'{what}: {t.shape[1]} values per layer for {self.K} samples')
+        return t.contiguous()
+
+    def set_thicknesses(self, d):
+        t = self._table(d, self.rdtype, 'thicknesses')
+        if t.shape[0] != self.L:
+            raise ValueError(f'thicknesses describe {t.shape[0]} layers, indices {self.L}')
+        self.d = t
+        return self
+
+    def args(self):
+        """the operand block of both entry points, after (dtype, pol, ..., K, L)"""
+        def ss(t):
+            return 0 if t.numel() == 1 and self.K != 1 else 1
+
+        def table(t):
+            if self.L == 0:
+                return [L.ptr(None), 0, 0]
+            per = t.shape[1] != 1 or self.K == 1
+            return [L.ptr(t), t.shape[1], 1 if per else 0]
+        return ([L.ptr(self.wvl), ss(self.wvl), L.ptr(self.theta), ss(self.theta)] + table(self.n) + table(self.d)
+                + [L.ptr(self.nsub), ss(self.nsub), L.ptr(self.n0), ss(self.n0)])
+
+
+_TF_POLS = {'s': L.PM_TF_S, 'p': L.PM_TF_P, 'both': L.PM_TF_BOTH}
+
+
+def tf_stack(op, pol, t_convention=L.PM_TF_T_STACK, want=()):
+    """pm_tf_stack on a TfOperands: a dict with r and t and whatever `want` names of 'R', 'T', 'fields' (E and H) and 'A'.  pol is
+    's', 'p' or 'both'; every array has the leading axis of polarisations (1 or 2), then boundaries or layers, then the K samples.
+    One launch."""
+    code = _TF_POLS[pol]
+    NP, K, Ly = (2 if pol == 'both' else 1), op.K, op.L
+    dev = L.device()
+    out = {'r': torch.empty((NP, K), dtype=op.cdtype, device=dev), 't': torch.empty((NP, K), dtype=op.cdtype, device=dev)}
+    if 'R' in want:
+        out['R'] = torch.empty((NP, K), dtype=op.rdtype, device=dev)
+    if 'T' in want:
+        out['T'] = torch.empty((NP, K), dtype=op.rdtype, device=dev)
+    if 'fields' in want:
+        out['E'] = torch.empty((NP, Ly + 1, K), dtype=op.cdtype, device=dev)
+        out['H'] = torch.empty((NP, Ly + 1, K), dtype=op.cdtype, device=dev)
+    if 'A' in want:
+        out['A'] = torch.empty((NP, Ly, K), dtype=op.rdtype, device=dev)
+    if K:
+        lib = L.load()
+        L.check(lib.pm_tf_stack(L._COMPLEX_CODE[op.cdtype], code, int(t_convention), K, Ly, *op.args(), L.ptr(out['r']), L.ptr(out['t']),
+                                L.ptr(out.get('R')), L.ptr(out.get('T')), L.ptr(out.get('E')), L.ptr(out.get('H')), L.ptr(out.get('A')),
+                                L.stream_ptr()))
+    return out
+
+
+def tf_thickness_grad(op, pol, dR=None, dT=None, grad=None):
+    """pm_tf_thickness_grad on a TfOperands: the (L,) gradient of sum_k F with respect to the thicknesses from the seeds dR, dT (K
+    values shared by the polarisations, or (2, K) with pol 'both'; either may be None).  Added to `grad` when that is given.  Two
+    launches; the sum over samples is in double and in a fixed order."""
+    code = _TF_POLS[pol]
+    NP, K, Ly = (2 if pol == 'both' else 1), op.K, op.L
+    acc = grad is not None
+    if acc:
+        if grad.dtype != op.rdtype or grad.numel() != Ly or not grad.is_contiguous() or grad.device != L.device():
+            raise ValueError('thickness gradient: `grad` must be a contiguous device tensor of one real value per layer')
+    else:
+        grad = torch.zeros(Ly, dtype=op.rdtype, device=L.device())
+    ps = 0
+
+    def seed(s):
+        nonlocal ps
+        if s is None:
+            return None
+        t = L.as_device(s, op.rdtype).reshape(-1)
+        if t.numel() == NP * K and NP == 2:
+            ps = K
+        elif t.numel() != K:
+            raise ValueError(f'a seed has {t.numel()} values for {K} samples')
+        return t
+    r, t = seed(dR), seed(dT)
+    if r is not None and t is not None and r.numel() != t.numel():
+        raise ValueError('dR and dT must have the same shape')
+    if K == 0 or Ly == 0 or (r is None and t is None):
+        return grad
+    lib = L.load()
+    cd = L._COMPLEX_CODE[op.cdtype]
+    ws = L.workspace(int(lib.pm_tf_thickness_grad_workspace(cd, code, K, Ly)))
+    L.check(lib.pm_tf_thickness_grad(cd, code, K, Ly, *op.args(), L.ptr(r), L.ptr(t), ps, int(acc), L.ptr(grad), L.ptr(ws), ws.numel(),
+                                     L.stream_ptr()))
+    return grad
+
+
 def ceil_half(d):
     return math.ceil(d / 2)
 
