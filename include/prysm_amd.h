@@ -810,15 +810,16 @@ int pm_plan_prepare(int32_t dtype, int64_t n);   /* build + cache the tables of 
                                                   * transform of a length otherwise does it, with a blocking upload that a hipGraph capture
                                                   * cannot record */
 void pm_shutdown(void);            /* free cached tables */
-/* performance knobs (they choose among equivalent routes and tilings; results agree to rounding): "col_var", "row_var" pick kernel
- * tilings, "nt_in" / "nt_out" in {0,1} make the input loads / output stores non-temporal, "fold", "log_k", "batch_ws_mib",
- * "gemm_3m", "gemm_min_wgs" tune the engine and the GEMM; routing of awkward lengths: "blue_min" (shortest length on the Bluestein
+/* performance knobs (they choose among equivalent routes and tilings; results agree to rounding): "col_var" picks the column
+ * pass's tiling, "nt_in" / "nt_out" in {0,1} make the input loads / output stores non-temporal, "fold", "log_k", "batch_ws_mib",
+ * "gemm_min_wgs" tune the engine and the GEMM; routing of awkward lengths: "blue_min" (shortest length on the Bluestein
  * path, 0 = off), "blue_2d" / "blue_fuse" (both-axes form; chirp multiplies inside the chain), "big_native_log" (log2 of the longest
  * length given to the engine as it is; the GPU tests lower it to run the 16384-point path on small arrays); real inputs: "r2c"
  * (Hermitian path: 0 never, 1 where it pays, 2 wherever legal), "herm_t" (its transposed form, real-input column transforms first:
  * -1 where it measured faster, 0 never, 1 wherever legal) with "herm_t_fold" (its column pass as planes of half-height tiles).  The full list with
  * defaults and measurements: struct Tuning in prysm_amd/csrc/pm_internal.h.  Also read once from the environment:
- * PM_TUNE="nt_in=1,fold=0". */
+ * PM_TUNE="nt_in=1,fold=0".  Knobs whose variants left the library keep their names: the one value each still accepts returns 0,
+ * any other PM_ERR_UNSUPPORTED (a PM_TUNE entry of that kind is skipped). */
 int pm_set_tuning(const char* key, int32_t value);
 /* the same knob for the CALLING host thread only: its first call gives the thread a private copy of the process-wide values, which
  * every later library call on that thread reads; pm_reset_tuning_local() returns the thread to the shared values.  This is the form

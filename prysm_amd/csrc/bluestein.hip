@@ -115,7 +115,6 @@ int blue_rows(const DirectIn<T>& in, cx<T>* out, int64_t out_ld, void* scratch, 
     const cx<T>* tw = twiddles<T>(mb, &err);
     if (!tw) return err;
     const cx<T>*w = tab, *bf = tab + n;
-    const int dt = sizeof(T) == 4 ? PM_C64 : PM_C128;
     cx<T>* a = reinterpret_cast<cx<T>*>(scratch);
     cx<T>* b = reinterpret_cast<cx<T>*>(static_cast<char*>(scratch) + align256(size_t(nseq) * size_t(n) * sizeof(cx<T>)));
 
@@ -123,14 +122,14 @@ int blue_rows(const DirectIn<T>& in, cx<T>* out, int64_t out_ld, void* scratch, 
     {   // A = FFT_MB(pad(a))
         RowLoadNat<T> lp{a, n, AxisMap{mb, n, 0, 0}, nseq, 0, 0};
         RowStoreNat<T> sp{b, mb, AxisMap{mb, mb, 0, 0}, nseq, 0, T(1), 0, AxisMap{1, 1, 0, 0}};
-        const int rc = launch_row_nat<T>(lg, row_variant(dt, lg), lp, sp, tw, nseq, 0, st);
+        const int rc = launch_row_nat<T>(lg, lp, sp, tw, nseq, 0, st);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(blue_mul_rows_kernel<T>, grid_for(int64_t(nseq) * mb), dim3(256), 0, st, b, int64_t(mb), nseq, mb, bf);
     if (o) {   // 1-D API: the first n bins back into `a`, then through the output view
         RowLoadNat<T> lp{b, mb, AxisMap{mb, mb, 0, 0}, nseq, 1, 0};
         RowStoreNat<T> sp{a, n, AxisMap{mb, n, 0, 0}, nseq, 1, T(1), 0, AxisMap{1, 1, 0, 0}};
-        const int rc = launch_row_nat<T>(lg, row_variant(dt, lg), lp, sp, tw, nseq, 0, st);
+        const int rc = launch_row_nat<T>(lg, lp, sp, tw, nseq, 0, st);
         if (rc) return rc;
         hipLaunchKernelGGL(blue_post_rows_out_kernel<T>, grid_for(int64_t(nseq) * n), dim3(256), 0, st, a, n, w, *o);
         return int(hipGetLastError());
@@ -138,7 +137,7 @@ int blue_rows(const DirectIn<T>& in, cx<T>* out, int64_t out_ld, void* scratch, 
     {   // c = IFFT_MB(A .* B), first n bins straight into the caller's rows
         RowLoadNat<T> lp{b, mb, AxisMap{mb, mb, 0, 0}, nseq, 1, 0};
         RowStoreNat<T> sp{out, out_ld, AxisMap{mb, n, 0, 0}, nseq, 1, T(1), 0, AxisMap{1, 1, 0, 0}};
-        const int rc = launch_row_nat<T>(lg, row_variant(dt, lg), lp, sp, tw, nseq, 0, st);
+        const int rc = launch_row_nat<T>(lg, lp, sp, tw, nseq, 0, st);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(blue_mul_rows_kernel<T>, grid_for(int64_t(nseq) * n), dim3(256), 0, st, out, out_ld, nseq, n, w);

@@ -55,7 +55,6 @@ int pm_fft2_spectral(const pm_fft2_desc* d, int32_t count, const double* k, cons
         Spectral w{};
         w.nb = count - b0 < g ? count - b0 : g;
         w.fstride = int64_t(p.ws_field / (d->dtype == PM_C64 ? sizeof(cx<float>) : sizeof(cx<double>)));
-        w.mode = tuning().spectral_mode;
         for (int i = 0; i < w.nb; ++i) {
             w.w[i] = weight[b0 + i];
             w.k2[i] = k[b0 + i] / two_pi;

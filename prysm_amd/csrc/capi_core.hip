@@ -1,4 +1,6 @@
 // Error text, twiddle / plan tables behind a mutex, tuning knobs (process-wide and per thread), device queries -- and the entry points that only touch those.
+#include <climits>
+
 #include "capi_internal.h"
 
 namespace pm {
@@ -126,20 +128,31 @@ static const cx<T>* blue_table_get(int64_t n, int* err) {
 template <> const cx<float>* blue_tables<float>(int64_t n, int* err) { return blue_table_get<float>(n, err); }
 template <> const cx<double>* blue_tables<double>(int64_t n, int* err) { return blue_table_get<double>(n, err); }
 
-static void tune_set(Tuning& t, const char* key, size_t klen, int v) {
+// Knobs whose variants measured slower and left the sources in round 5 (experiments/README.md has the list, the logs and the patch that
+// brings them back): the name and the one value it still accepts -- what the library does anyway.  Any other value is refused instead of
+// silently running something else.  kAny: a knob that qualified a removed variant or is ignored; every value is accepted.
+constexpr int kAny = INT_MIN;
+static const struct { const char* name; int accepted; } kRetired[] = {
+    {"mix_fold", 0}, {"mix_pers", 0}, {"mix_ablate", 0}, {"two_units", 0}, {"engine_p8", 0}, {"spectral2", 0}, {"spectral2_keep", kAny},
+    {"spectral2_min_log", kAny}, {"row_var", kAny}, {"gemm_3m", 1}, {"gemm_bm", 64}, {"gemm_bk", 0}, {"spectral_mode", 3},
+};
+
+// `key` (klen characters) = v: 1 set, 0 not a knob or a retired one at its accepted value (nothing to set), -1 refused (a retired value,
+// also of the knobs that keep some of their forms: colmul_mode 1 / 2, gemm_wk bits 1 / 2).  Every way in -- PM_TUNE, pm_set_tuning,
+// pm_set_tuning_local -- goes through here.
+static int tune_set(Tuning& t, const char* key, size_t klen, int v) {
     auto is = [&](const char* k) { return strlen(k) == klen && !strncmp(key, k, klen); };
+    for (const auto& r : kRetired)
+        if (is(r.name)) return (r.accepted == kAny || v == r.accepted) ? 0 : -1;
+    if ((is("colmul_mode") && (v == 1 || v == 2)) || (is("gemm_wk") && (v & 6))) return -1;
     if (is("col_var")) t.col_var = v;
     else if (is("log_k")) t.log_k = v > 12 ? 12 : v;   // < 0: auto; log2(N / tile width) makes the intermediate natural (row-major)
     else if (is("row_log_g")) t.row_log_g = v < 0 ? 0 : (v > 3 ? 3 : v);
-    else if (is("row_var")) t.row_var = v;
     else if (is("stagger_group")) t.stagger_group = v ? 1 : 0;
     else if (is("col_log_g")) t.col_log_g = v;
-    else if (is("gemm_bk")) t.gemm_bk = v;
-    else if (is("gemm_bm")) t.gemm_bm = v;
     else if (is("gemm_dma")) t.gemm_dma = v ? 1 : 0;
     else if (is("gemm_dma_wgs")) t.gemm_dma_wgs = v < 1 ? 1 : v;
     else if (is("gemm_tile")) t.gemm_tile = (v == 64 || v == 128) ? v : 0;
-    else if (is("gemm_3m")) t.gemm_3m = v ? 1 : 0;
     else if (is("gemm_wk")) t.gemm_wk = v & 7;
     else if (is("gemm_min_wgs")) t.gemm_min_wgs = v < 1 ? 1 : v;
     else if (is("nt_in")) t.nt_in = v;
@@ -150,21 +163,16 @@ static void tune_set(Tuning& t, const char* key, size_t klen, int v) {
     else if (is("mix_min")) t.mix_min = v < 18 ? 18 : v;
     else if (is("mix_fused")) t.mix_fused = v ? 1 : 0;
     else if (is("mix_pad")) t.mix_pad = v ? 1 : 0;
-    else if (is("two_units")) t.two_units = v & 3;
-    else if (is("mix_ablate")) t.mix_ablate = v & 15;
     else if (is("fft_stagger")) t.fft_stagger = v < 0 ? -1 : (v > 164 ? 164 : v);
     else if (is("fft_stagger_r2c")) t.fft_stagger_r2c = v < 0 ? 0 : (v > 164 ? 164 : v);
     else if (is("fft_stagger_herm")) t.fft_stagger_herm = v < 0 ? -1 : (v > 164 ? 164 : v);
     else if (is("fft_stagger_mid")) t.fft_stagger_mid = v < 0 ? -1 : (v > 64 ? 64 : v);
     else if (is("fft_stagger_col")) t.fft_stagger_col = v < 0 ? -1 : (v > 164 ? 164 : v);
-    else if (is("mix_fold")) t.mix_fold = v != 0;
-    else if (is("mix_pers")) t.mix_pers = v != 0;
     else if (is("mix_engine")) t.mix_engine = v ? 1 : 0;
     else if (is("ce_rows_seqs")) t.ce_rows_seqs = v < 0 ? 0 : v;
     else if (is("ce_cols_seqs")) t.ce_cols_seqs = v < 0 ? 0 : v;
     else if (is("ce_log_g")) t.ce_log_g = v;
     else if (is("mix_stagger")) t.mix_stagger = v < 0 ? 0 : (v > 64 ? 64 : v);
-    else if (is("engine_p8")) t.engine_p8 = v & 7;
     else if (is("mix_maxr")) t.mix_maxr = (v < 2 || v > 20) ? 20 : v;
     else if (is("mix_log_g")) t.mix_log_g = v;
     else if (is("mix_seqs")) t.mix_seqs = v < 0 ? 0 : v;
@@ -179,15 +187,13 @@ static void tune_set(Tuning& t, const char* key, size_t klen, int v) {
     else if (is("herm_t_fold")) t.herm_t_fold = v < 0 ? -1 : (v ? 1 : 0);
     else if (is("herm_t_rowvar")) t.herm_t_rowvar = v;
     else if (is("spectral")) t.spectral = v;
-    else if (is("spectral_mode")) t.spectral_mode = v & 3;
     else if (is("spectral_area_log")) t.spectral_area_log = v;
-    else if (is("spectral2")) t.spectral2 = (v == 2 || v == 3 || v == 4) ? v : 0;
-    else if (is("spectral2_keep")) t.spectral2_keep = v ? 1 : 0;
-    else if (is("spectral2_min_log")) t.spectral2_min_log = v;
     else if (is("blue_min")) t.blue_min = v < 0 ? 0 : v;
     else if (is("blue_2d")) t.blue_2d = v ? 1 : 0;
     else if (is("blue_fuse")) t.blue_fuse = v ? 1 : 0;
     else if (is("big_native_log")) t.big_native_log = v < 1 ? 1 : (v > kEngineMaxLog ? kEngineMaxLog : v);
+    else return 0;
+    return 1;
 }
 
 // The process-wide defaults (PM_TUNE, pm_set_tuning) and, per host thread, an optional private copy (pm_set_tuning_local): the
@@ -197,7 +203,7 @@ static void tune_set(Tuning& t, const char* key, size_t klen, int v) {
 static Tuning& tuning_global() {
     static Tuning t = [] {
         Tuning x;
-        const char* e = getenv("PM_TUNE");   // e.g. PM_TUNE="nt_in=1,fold=0"
+        const char* e = getenv("PM_TUNE");   // e.g. PM_TUNE="nt_in=1,fold=0"; an entry the setters would refuse is skipped
         while (e && *e) {
             const char* eq = strchr(e, '=');
             if (!eq) break;
@@ -242,37 +248,24 @@ extern "C" {
 
 int pm_version(void) { return PM_VERSION; }
 
-// Variants that measured slower were built behind -DPM_EXPERIMENTS through round 4 and left the sources in round 5 (experiments/README.md
-// has the list, the logs and the patch that brings them back): the library refuses the knob values that selected them instead of
-// silently running something else.
-static bool experiment_only(const char* key, int v) {
-    auto is = [&](const char* k) { return !strcmp(key, k); };
-    return (is("spectral_mode") && (v & 3) != 3) || (is("gemm_3m") && !v) || (is("gemm_bm") && v == 128) || (is("gemm_bk") && v == 32) ||
-           (is("colmul_mode") && (v == 1 || v == 2)) || (is("gemm_wk") && (v & 6)) || (is("spectral2") && v != 0) || (is("two_units") && v != 0) || (is("engine_p8") && v != 0) ||
-           (is("mix_ablate") && v != 0) || (is("mix_pers") && v != 0) || (is("mix_fold") && v != 0);
-}
-
 int pm_set_tuning(const char* key, int32_t value) {
     if (!key) return fail(PM_ERR_ARG, "pm_set_tuning: null key");
-    if (experiment_only(key, value))
-        return fail(PM_ERR_UNSUPPORTED, "pm_set_tuning: %s = %d selects a variant that lost its measurement and is no longer in the library (experiments/README.md)", key,
-                    int(value));
     static std::mutex mu;      // writers of the process-wide defaults are serialised; a thread that needs its own values while others
     std::lock_guard<std::mutex> lk(mu);     // run takes pm_set_tuning_local
-    tune_set(tuning_global(), key, strlen(key), value);
+    if (tune_set(tuning_global(), key, strlen(key), value) < 0)
+        return fail(PM_ERR_UNSUPPORTED, "pm_set_tuning: %s = %d selects a variant that lost its measurement and is no longer in the library (experiments/README.md)", key,
+                    int(value));
     return 0;
 }
 
 int pm_set_tuning_local(const char* key, int32_t value) {
     if (!key) return fail(PM_ERR_ARG, "pm_set_tuning_local: null key");
-    if (experiment_only(key, value))
+    Tuning t = tuning();        // the thread's copy starts from the defaults of this moment; a refused value leaves it as it was
+    if (tune_set(t, key, strlen(key), value) < 0)
         return fail(PM_ERR_UNSUPPORTED, "pm_set_tuning_local: %s = %d selects a variant that lost its measurement and is no longer in the library (experiments/README.md)",
                     key, int(value));
-    if (!g_tune_local_on) {
-        g_tune_local = tuning_global();     // the thread's copy starts from the defaults of this moment
-        g_tune_local_on = true;
-    }
-    tune_set(g_tune_local, key, strlen(key), value);
+    g_tune_local = t;
+    g_tune_local_on = true;
     return 0;
 }
 

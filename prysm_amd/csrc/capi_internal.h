@@ -41,7 +41,6 @@ struct Fft2Plan {
     bool fold;            // one radix-2 step of the column transform is taken in the row pass (RowStoreFold): the column
                           // pass then runs two planes of M/2-point tiles; on the transposed Hermitian form (r2c_t) in the column pass's load
     bool mix_n, mix_m;    // the row / column transforms take the mixed-radix kernel (composite lengths, fft_mixed.hip)
-    bool mix_fold;        // ... with one radix-2 step of the column transform folded into the row pass (MixRowOut fold_h): half-length column tiles
     int64_t w_ld;         // row pitch of the NATURAL intermediate (tc == 0), in elements: N, or N rounded up to whole 128 B lines when the
                           // column pass is the mixed-radix kernel -- its 32 / 64 B pieces then share lines only inside one XCD group
                           // (3000 complex64 columns: rows of 24000 B put every other row half a line off and the pass read 1.52x its bytes)
@@ -52,8 +51,9 @@ struct Fft2Plan {
     bool blue2d;          // both axes: chirp multiply -> ONE fused fft2 x (B1 (x) B2) ifft2 chain of size MB1 x MB2 -> chirp multiply
                           // (blue2d_run); the workspace is then [a (M x N) | c (M x N) | workspace of the fused chain]
     bool blue_fuse;       // ... with the chirp multiplies inside the chain's first / last row pass (blue2d_fused_run)
-    // launch choices (the runner reads these, not the knobs): log2 of the layout tile, sibling groups, row tiling, streaming loads / stores
-    int ltl, row_log_g, col_log_g, row_var, nt_in, nt_out;
+    // launch choices (the runner reads these, not the knobs): log2 of the layout tile, sibling groups, streaming loads / stores
+    int ltl, row_log_g, col_log_g, nt_in, nt_out;
+    int hermt_row_var;    // r2c_t: tiling of its row pass at 4096 complex64 points (launch_row_hermt): 4 two rows per thread, 0 one row per workgroup
 };
 
 // ---------------------------------------------------------------- fused fft2 -> multiply -> ifft2

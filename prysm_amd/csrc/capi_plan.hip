@@ -118,14 +118,14 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
     const int64_t rows = d->in_y.len;   // only stored input rows are transformed in pass 1
     p.fold = false;
     p.w_ld = N;
-    p.row_var = p.logn >= 0 ? row_variant(d->dtype, p.logn) : 0;
+    p.hermt_row_var = 0;
     p.r2c = allow_r2c && p.logn >= 0 && p.logm >= 0 && r2c_legal(d, p.logn, p.logm);
     p.r2c_t = p.r2c && hermt_legal(d, p.logn, p.logm);
     if (p.r2c_t) {
         p.col_var = p.tc = p.log_k = 0;
         p.ws_bytes = size_t(M / 2) * size_t(N) * es;      // rows u < M/2 of the column spectra, row-major (row 0 carries u = 0 and u = M/2)
         p.fold = hermt_fold(p.logm);
-        if (tuning().herm_t_rowvar >= 0) p.row_var = tuning().herm_t_rowvar;
+        p.hermt_row_var = tuning().herm_t_rowvar == 0 ? 0 : 4;      // knob herm_t_rowvar; default: the complex path's tiling (fft_kernels.h built_row_var)
         // adjacent tiles read the two halves of the input's 128 B lines and write adjacent lines of the intermediate: siblings on one XCD
         // (profiles/r06/exp_herm_t_log_g.log, mtf_from_psf us at col_log_g 0 .. 5: 4096^2 fp32 folded 75.9 68.5 69.7 69.3 67.9 68.1 -- the pass reads
         // 64 B pieces of a row-major array, neighbours share its 128 B lines --; 2048^2 (128 tiles, half the CUs) 31.9 33.6 33.7 33.8 34.2 34.4)
@@ -207,7 +207,7 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
     }
     if (!(p.big_rn && p.big_rm && (p.big_rn > 1 || p.big_rm > 1)) || (d->flags & (PM_FLAG_PASS1_ONLY | PM_FLAG_PASS2_ONLY | PM_FLAG_SYNTH_INPUT)))
         p.big_rn = p.big_rm = 0;
-    p.mix_n = p.mix_m = p.mix_fold = false;
+    p.mix_n = p.mix_m = false;
     if (p.big_rn) {   // [Z: R_n planes of M x N/R_n | F (and the pre-processed rows before it): the same size]
         p.tc = 0;
         p.fold = false;
@@ -221,22 +221,6 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
     const bool mixfit = mix_fits(N, d->in_ld, es, false) && mix_fits(M, p.w_ld, es, true) && mix_fits(M, d->out_ld, es, true);
     p.mix_n = mixfit && p.logn < 0 && use_mix(N);
     p.mix_m = mixfit && p.logm < 0 && use_mix(M);
-    // FOLD on composite grids (round 4; knob mix_fold, experiment builds only -- measured slower, fft_mixed.h MixRowOut): where four columns of M points fill a CU's LDS the column kernel runs one workgroup per CU, whose
-    // load / butterfly / store phases nothing overlaps (fft_mixed_kernels.h).  With the radix-2 step of the column transform taken by the
-    // row pass (rows in pairs (g, g + M/2)) the column tiles are half as tall and two or three workgroups share a CU.  Needs every row
-    // stored, rotations of 0 or M/2 on the way in and an even one on the way out, no multiplier, one field.
-    {
-        const int64_t H = M / 2;
-        // the tile the unfolded column pass would take (mix_cols_impl: four columns, eight of mid-size complex64, fewer when they do not fit)
-        const size_t per = size_t(M) * es, hard = size_t(156) * 1024;
-        size_t tc0 = (es == 8 && per > size_t(10) * 1024 && 8 * per <= hard) ? 8 : 4;
-        while (tc0 > 1 && tc0 * per > hard) tc0 /= 2;
-        p.mix_fold = tuning().mix_fold && p.mix_n && p.mix_m && (M % 2) == 0 && use_mix(H) && tc0 * per > size_t(80) * 1024 &&
-                     d->in_y.len == M && d->in_y.off == 0 && (d->in_y.shift == 0 || d->in_y.shift == H) && d->out_y.len == M && d->out_y.off == 0 &&
-                     (d->out_y.shift % 2) == 0 && d->mul_kind == PM_MUL_NONE &&
-                     !(d->flags & (PM_FLAG_PASS1_ONLY | PM_FLAG_PASS2_ONLY)) && mix_fits(N, H * d->in_ld, es, false) &&
-                     (!(d->flags & PM_FLAG_SYNTH_INPUT) || !d->synth_amp || mix_fits(N, H * d->synth_amp_ld, es, false));
-    }
     p.blue_n = p.logn < 0 && use_blue(N, mixfit);
     p.blue_m = p.logm < 0 && use_blue(M, mixfit);
     p.blue_off = (p.ws_bytes + 255) & ~size_t(255);
@@ -479,7 +463,7 @@ bool ce_rows_axis(const pm_fft2_desc* d, const Fft2Plan& p) {
     const bool f32 = d->dtype == PM_C64;
     const size_t es = f32 ? 8 : 16;
     const int64_t N = d->in_x.n;
-    return p.mix_n && !p.mix_fold && tuning().mix_engine && !(d->flags & PM_FLAG_REAL_INPUT) && (f32 || !(d->flags & PM_FLAG_SYNTH_INPUT)) &&
+    return p.mix_n && tuning().mix_engine && !(d->flags & PM_FLAG_REAL_INPUT) && (f32 || !(d->flags & PM_FLAG_SYNTH_INPUT)) &&
            (f32 ? ce_has_plan<float>(int(N)) : ce_has_plan<double>(int(N))) && ce_fits32(kCeMaxSeqs * d->in_ld + 2 * N, es) &&
            ce_fits32(kCeMaxSeqs * p.w_ld + 2 * N, es);
 }
@@ -488,7 +472,7 @@ bool ce_cols_axis(const pm_fft2_desc* d, const Fft2Plan& p) {
     const size_t es = f32 ? 8 : 16;
     const int64_t M = d->in_y.n, N = d->in_x.n;
     const bool whole_out = d->out_y.off == 0 && d->out_y.len == M && d->out_x.off == 0 && d->out_x.len == N;
-    return p.mix_m && !p.mix_fold && tuning().mix_engine && whole_out && d->mul_kind == PM_MUL_NONE && d->epilogue <= PM_EPI_ABS2_ACCUM &&
+    return p.mix_m && tuning().mix_engine && whole_out && d->mul_kind == PM_MUL_NONE && d->epilogue <= PM_EPI_ABS2_ACCUM &&
            (f32 ? ce_has_plan<float>(int(M)) : ce_has_plan<double>(int(M))) && ce_fits32(2 * M * p.w_ld + kCeMaxSeqs, es) &&
            ce_fits32(2 * M * d->out_ld + N, es);
 }

@@ -88,7 +88,7 @@ static int fft2_run_chunk(const pm_fft2_desc* d, const Fft2Plan& p, const void* 
         RowLoadNat<T> lp{W, N, AxisMap{int(N), int(N), 0, 0}, int(M / 2), 0, 0, 0};
         HermTRowStore<T> rs{out, d->out_ld, int(M), int(N), int(d->out_y.shift), int(d->out_x.shift), d->epilogue, T(d->scale),
                             (d->flags & PM_FLAG_NORM_DC) ? 1 : 0, W, d->in_x.shift == N / 2 ? 1 : 0, int(M / 2)};
-        rc = launch_row_hermt<T>(p.logn, p.row_var, lp, rs, twn, p.row_log_g, st);
+        rc = launch_row_hermt<T>(p.logn, p.hermt_row_var, lp, rs, twn, p.row_log_g, st);
         if (rc) return rc < 0 ? fail(PM_ERR_UNSUPPORTED, "pm_fft2: internal: no transposed Hermitian row kernel for %lld points", (long long)N) : rc;
         return 0;
     }
@@ -153,10 +153,10 @@ static int fft2_run_chunk(const pm_fft2_desc* d, const Fft2Plan& p, const void* 
                 rc = launch_row_fold<T>(p.logn, lp, sp, tw, int(M / 2), p.row_log_g, st, 1);
             } else if (p.tc) {
                 RowStoreTiled<T> sp{W, rows, p.ltl, wstride};
-                rc = launch_row_tiled<T>(p.logn, p.row_var, lp, sp, tw, rows, p.row_log_g, st, nb);
+                rc = launch_row_tiled<T>(p.logn, lp, sp, tw, rows, p.row_log_g, st, nb);
             } else {
                 RowStoreNat<T> sp{W, p.w_ld, AxisMap{int(N), int(N), 0, 0}, rows, 0, T(1), 0, AxisMap{1, 1, 0, 0}};
-                rc = launch_row_nat<T>(p.logn, p.row_var, lp, sp, tw, rows, 0, st);
+                rc = launch_row_nat<T>(p.logn, lp, sp, tw, rows, 0, st);
             }
             if (rc) return rc;
         } else {
@@ -177,15 +177,10 @@ static int fft2_run_chunk(const pm_fft2_desc* d, const Fft2Plan& p, const void* 
                     return fail(PM_ERR_UNSUPPORTED, "pm_fft2: PM_FLAG_SYNTH_INPUT: amplitude pitch beyond 2^24 elements");
             }
             int rc;
-            if (p.mix_n && p.mix_fold) {
-                const cx<T>* twm = twiddles<T>(M, &err);
-                if (!twm) return err;
-                const MixFold<T> mf{int(M / 2), d->in_y.shift == M / 2 ? 1 : 0, twm};
-                rc = mix_rows<T>(di, W, p.w_ld, st, nullptr, &mf);
-            } else if (p.mix_n) {
+            if (p.mix_n) {
                 di.nb = nb;                 // a stack (fft2_run: only where both passes are mixed-radix and the view is plain)
                 di.bstride = d->in_bstride;
-                rc = mix_rows<T>(di, W, p.w_ld, st, nullptr, nullptr, wstride);
+                rc = mix_rows<T>(di, W, p.w_ld, st, nullptr, wstride);
             } else if (p.blue_n) {
                 rc = blue_rows<T>(di, W, p.w_ld, static_cast<char*>(ws) + p.blue_off, st);
             } else {
@@ -226,22 +221,6 @@ static int fft2_run_chunk(const pm_fft2_desc* d, const Fft2Plan& p, const void* 
         const int ntiles = int((N + tc - 1) / tc);
         ColLoadNat<T> cl{W, p.w_ld, to_map(d->in_y), int(N), 0, (p.w_ld % 2 == 0) ? 1 : 0};
         return launch_col_nat<T>(p.logm, 0, cl, cs, tw, ntiles, p.col_log_g, st);
-    }
-    if (p.mix_m && p.mix_fold) {
-        // two planes of M/2-point column transforms: plane b holds the output rows 2 k + b -- the output seen with a doubled leading
-        // dimension, plane 1 one row further (as the engine's fold above)
-        const int H = int(M / 2);
-        const size_t oes = d->epilogue == PM_EPI_NONE ? sizeof(cx<T>) : sizeof(T);
-        for (int b = 0; b < 2; ++b) {
-            DirectIn<T> dp{W + int64_t(b) * H * p.w_ld, 1, p.w_ld, AxisMap{H, H, 0, 0}, int(N), 0};
-            ColStoreNat<T> cp = cs;
-            cp.dst = static_cast<char*>(cs.dst) + size_t(b) * size_t(d->out_ld) * oes;
-            cp.ld = 2 * d->out_ld;
-            cp.ay = AxisMap{H, H, 0, int(d->out_y.shift / 2)};
-            const int rc = mix_cols<T>(dp, cp, st);
-            if (rc) return rc;
-        }
-        return 0;
     }
     DirectIn<T> di{W, 1, p.w_ld, to_map(d->in_y), int(N), 0};   // sequence = column c at W[c], element stride = the pitch of the intermediate
     if (p.mix_m) {
@@ -327,7 +306,7 @@ static int fused_run_chunk(const pm_fft2_desc* d, const FusedPlan& p, const void
         RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), d->in_ld, to_map(d->in_x), rows, 0, p.nt_in, d->in_bstride};
         set_input_mode(lp, d);
         RowStoreTiled<T> sp{W1, rows, p.ltl, wstride};
-        int rc = launch_row_tiled<T>(p.logn, row_variant(d->dtype, p.logn), lp, sp, twN, rows, p.row_log_g, st, nb);
+        int rc = launch_row_tiled<T>(p.logn, lp, sp, twN, rows, p.row_log_g, st, nb);
         if (rc) return rc;
     }
     // pass B: column FFT, x H, column IFFT (unnormalised) -> tiled W2 (all M rows)
@@ -353,7 +332,7 @@ static int fused_run_chunk(const pm_fft2_desc* d, const FusedPlan& p, const void
     RowLoadTiled<T> rl{W2, int(M), p.ltl, row0, nrun, 1, wstride};
     RowStoreNat<T> rs{reinterpret_cast<cx<T>*>(out), d->out_ld, to_map(d->out_x), nrun, 1, T(d->scale), 1, oy, d->out_bstride};
     rs.nt = p.nt_out;
-    return launch_row_from_tiled<T>(p.logn, row_variant(d->dtype, p.logn), rl, rs, twN, nrun, st, nb);
+    return launch_row_from_tiled<T>(p.logn, rl, rs, twN, nrun, st, nb);
 }
 
 // the composite-grid chain (plan_fused_mix)
@@ -385,7 +364,7 @@ static int fused_mix_run(const pm_fft2_desc* d, const FusedPlan& p, const void* 
         RowLoadNat<T> lp{W2, p.w_ld, AxisMap{int(N), int(N), 0, 0}, int(M), 1, 0, 0};
         RowStoreNat<T> rs{reinterpret_cast<cx<T>*>(out), d->out_ld, to_map(d->out_x), int(M), 1, T(d->scale), 1, to_map(d->out_y), 0};
         rs.nt = p.nt_out;
-        return launch_row_nat<T>(p.logn, row_variant(d->dtype, p.logn), lp, rs, twN, int(M), 0, st);
+        return launch_row_nat<T>(p.logn, lp, rs, twN, int(M), 0, st);
     }
     // the mixed-radix row kernel writes sequence s to memory row s: the kept positions [off, off + len) of the rotated rows are at most
     // two runs of consecutive logical rows
@@ -487,7 +466,7 @@ static int blue2d_fused_run(const pm_fft2_desc* d, const Fft2Plan& p, const void
                                    (d->flags & PM_FLAG_REAL_INPUT) ? 1 : 0},
                        t1, t2, rows};
     RowStoreTiled<T> sp{W1, rows, fp.ltl, 0};
-    int rc = launch_row_chirp_tiled<T>(fp.logn, row_variant(d->dtype, fp.logn), lp, sp, twN, rows, fp.row_log_g, st);
+    int rc = launch_row_chirp_tiled<T>(fp.logn, lp, sp, twN, rows, fp.row_log_g, st);
     if (rc) return rc;
     // pass B: column FFT x (B1 (x) B2) x column IFFT -> tiled W2
     const int ntiles = int((N + fp.tc - 1) / fp.tc);
@@ -499,7 +478,7 @@ static int blue2d_fused_run(const pm_fft2_desc* d, const Fft2Plan& p, const void
     // pass C: inverse row transforms of the first n1 rows, bins [0, n2) x chirp through the caller's epilogue
     RowLoadTiled<T> rl{W2, rows, fp.ltl, 0, rows, 1, 0};
     RowStoreChirp<T> rs{make_colstore<T>(d, out, p.nt_out), t1, t2, int(n1), int(n2), 1};
-    return launch_row_tiled_chirp<T>(fp.logn, row_variant(d->dtype, fp.logn), rl, rs, twN, rows, st);
+    return launch_row_tiled_chirp<T>(fp.logn, rl, rs, twN, rows, st);
 }
 
 // ---------------------------------------------------------------- powers of two above the engine's longest transform
@@ -538,7 +517,7 @@ static int big2d_run(const pm_fft2_desc* d, const Fft2Plan& p, const void* in, v
         } else {
             RowLoadNat<T> lp{Y, np, AxisMap{np, np, 0, 0}, nseq, 0, 0};
             RowStoreNat<T> sp{Z, np, AxisMap{np, np, 0, 0}, nseq, 0, T(1), 0, AxisMap{1, 1, 0, 0}};
-            if ((rc = launch_row_nat<T>(lgn, row_variant(dt, lgn), lp, sp, twn, nseq, 0, st))) return rc;
+            if ((rc = launch_row_nat<T>(lgn, lp, sp, twn, nseq, 0, st))) return rc;
         }
     } else if (lgn < 0) {
         // a composite row length as it is (beside a column length that needs the step): the mixed-radix row kernel writes sequence s to
@@ -570,7 +549,7 @@ static int big2d_run(const pm_fft2_desc* d, const Fft2Plan& p, const void* in, v
             RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), d->in_ld, to_map(d->in_x), rows, conj, 0};
             set_input_mode(lp, d);
             RowStoreNat<T> sp{Z, N, AxisMap{int(N), int(N), 0, 0}, rows, 0, T(1), 1, AxisMap{int(M), int(M), 0, sh}};
-            if ((rc = launch_row_nat<T>(lgn, row_variant(dt, lgn), lp, sp, twn, rows, 0, st))) return rc;
+            if ((rc = launch_row_nat<T>(lgn, lp, sp, twn, rows, 0, st))) return rc;
         }
     }
     // ---- columns: plane m is an M x np matrix; F[(m R_m + r)] = FFT_{mp} down the columns of its rows r, r + R_m, ...
@@ -667,7 +646,7 @@ static int fft1_big(int conj, int axis, int64_t batch, const pm_axis* ti, const 
         const int nseq = R * nb;
         RowLoadNat<T> lp{Y, np, AxisMap{np, np, 0, 0}, nseq, 0, 0};
         RowStoreNat<T> sp{Z, np, AxisMap{np, np, 0, 0}, nseq, 0, T(1), 0, AxisMap{1, 1, 0, 0}};
-        if ((rc = launch_row_nat<T>(lg, row_variant(dt, lg), lp, sp, twp, nseq, 0, st))) return rc;
+        if ((rc = launch_row_nat<T>(lg, lp, sp, twp, nseq, 0, st))) return rc;
         return big_finish<T>(Z, nb, np, 1, R, twp, o, st);
     }
     o.ay = to_map(*to);
@@ -722,7 +701,7 @@ int fft1_run(int direction, int axis, int64_t batch, const pm_axis* ti, const pm
             const cx<T>* tw = twiddles<T>(n, &err);
             if (!tw) return err;
             RowLoadNat<T> lp{reinterpret_cast<const cx<T>*>(in), in_ld, to_map(*ti), int(batch), conj, 0};
-            return launch_row_nat<T>(lg, row_variant(sizeof(T) == 4 ? PM_C64 : PM_C128, lg), lp, sp, tw, int(batch), 0, st);
+            return launch_row_nat<T>(lg, lp, sp, tw, int(batch), 0, st);
         }
         DirectIn<T> di{reinterpret_cast<const cx<T>*>(in), in_ld, 1, to_map(*ti), int(batch), conj};
         if (use_mix(n) && mix_fits(n, in_ld, sizeof(cx<T>), false) && mix_fits(n, out_ld, sizeof(cx<T>), false)) return mix_rows<T>(di, nullptr, 0, st, &sp);
@@ -867,7 +846,7 @@ int fft2_spectral_group(const pm_fft2_desc* d, const Fft2Plan& p, const Spectral
     const cx<T>* twm = twiddles<T>(M, &err);
     if (!twm) return err;
     RowStoreTiled<T> sp{W, rows, p.ltl, 0};
-    if ((rc = launch_row_spectral<T>(p.logn, p.row_var, lp, sp, tw, rows, p.row_log_g, w, st))) return rc;
+    if ((rc = launch_row_spectral<T>(p.logn, lp, sp, tw, rows, p.row_log_g, w, st))) return rc;
     ColLoadTiled<T> cl{W, rows, to_map(d->in_y), ntiles, p.log_k, 0};
     return launch_col_spectral<T>(p.logm, cl, cs, twm, ntiles, p.col_log_g, w, st, 1);
 }

@@ -7,7 +7,7 @@
 // complex128 : v_mfma_f64_16x16x4_f64
 //
 // A complex product is THREE real MFMA chains (the "3M" form: P1 = Ar Br, P2 = Ai Bi, P3 = (Ar + Ai)(Br + Bi);
-// Cr = P1 - P2, Ci = P3 - P1 - P2; knob gemm_3m = 0: the four-chain form).  Operands stay interleaved (re, im) in global
+// Cr = P1 - P2, Ci = P3 - P1 - P2).  Operands stay interleaved (re, im) in global
 // memory and in LDS; conjugations are signs on the imaginary operands and in the epilogue.
 //
 // Two kernels:
@@ -121,13 +121,14 @@ struct Stager {
 };
 
 
-template <typename T, int BM, int BN, int BK, bool AKF, bool BKF, bool M3>
+template <typename T, int BK, bool AKF, bool BKF>
 __global__ void __launch_bounds__(256, 2) cgemm_kernel(int conjA, int conjB, int64_t M, int64_t N, int64_t K, int64_t ksplit,
                                                        T alpha, const cx<T>* __restrict__ A, int64_t lda,
                                                        const cx<T>* __restrict__ B, int64_t ldb, cx<T>* __restrict__ C,
                                                        int64_t ldc, int64_t slab_stride) {
     using MT = MfmaTraits<T>;
     constexpr int TM = MT::TM, KS = MT::KS, NR = MT::NR;
+    constexpr int BM = 64, BN = 64;              // workgroup tile
     constexpr int WM = BM / 2, WN = BN / 2;      // 2 x 2 waves
     constexpr int TI = WM / TM, TJ = WN / TM;    // MFMA tiles per wave
     constexpr int LDA_S = BM + 1, LDB_S = BN + 1;
@@ -150,10 +151,10 @@ __global__ void __launch_bounds__(256, 2) cgemm_kernel(int conjA, int conjB, int
     const int64_t kend = (kbeg + ksplit < K) ? kbeg + ksplit : K;
     const T sa = conjA ? T(-1) : T(1), sb = conjB ? T(-1) : T(1);
 
-    // M3 (three-multiplication complex product, "3M"): P1 = Ar Br, P2 = Ai Bi, P3 = (Ar + Ai)(Br + Bi);
+    // the three-multiplication complex product ("3M"): P1 = Ar Br, P2 = Ai Bi, P3 = (Ar + Ai)(Br + Bi);
     // Cr = P1 - P2, Ci = P3 - P1 - P2 -- three MFMA chains instead of four for two extra VALU adds per operand
-    // fragment; acc_r = P1, acc_i = P2 (M3) and acc_3 = P3.
-    typename MT::acc_t acc_r[TI][TJ], acc_i[TI][TJ], acc_3[M3 ? TI : 1][M3 ? TJ : 1];
+    // fragment; acc_r = P1, acc_i = P2 and acc_3 = P3.
+    typename MT::acc_t acc_r[TI][TJ], acc_i[TI][TJ], acc_3[TI][TJ];
 #pragma unroll
     for (int i = 0; i < TI; ++i)
 #pragma unroll
@@ -162,7 +163,7 @@ __global__ void __launch_bounds__(256, 2) cgemm_kernel(int conjA, int conjB, int
             for (int r = 0; r < NR; ++r) {
                 acc_r[i][j][r] = T(0);
                 acc_i[i][j][r] = T(0);
-                if constexpr (M3) acc_3[i][j][r] = T(0);
+                acc_3[i][j][r] = T(0);
             }
 
     SA stA;
@@ -223,37 +224,20 @@ __global__ void __launch_bounds__(256, 2) cgemm_kernel(int conjA, int conjB, int
             const int cur = (ks / KS) & 1;
             if (ks + KS < BK) read_frags(cur ^ 1, ks + KS);
             // conjugations: op(A) = Ar + i sa Ai, op(B) = Br + i sb Bi with sa, sb = +-1 (uniform)
-            if constexpr (M3) {
-                // P1 = Ar Br, P2 = Ai Bi (raw), P3 = (Ar + sa Ai)(Br + sb Bi); Cr = P1 - sa sb P2, Ci = P3 - P1 - sa sb P2
-                T as[TI], bs[TJ];
+            // P1 = Ar Br, P2 = Ai Bi (raw), P3 = (Ar + sa Ai)(Br + sb Bi); Cr = P1 - sa sb P2, Ci = P3 - P1 - sa sb P2
+            T as[TI], bs[TJ];
 #pragma unroll
-                for (int i = 0; i < TI; ++i) as[i] = a[cur][i].x + sa * a[cur][i].y;
+            for (int i = 0; i < TI; ++i) as[i] = a[cur][i].x + sa * a[cur][i].y;
 #pragma unroll
-                for (int j = 0; j < TJ; ++j) bs[j] = b[cur][j].x + sb * b[cur][j].y;
+            for (int j = 0; j < TJ; ++j) bs[j] = b[cur][j].x + sb * b[cur][j].y;
 #pragma unroll
-                for (int i = 0; i < TI; ++i)
+            for (int i = 0; i < TI; ++i)
 #pragma unroll
-                    for (int j = 0; j < TJ; ++j) {
-                        acc_r[i][j] = MT::mfma(a[cur][i].x, b[cur][j].x, acc_r[i][j]);
-                        acc_i[i][j] = MT::mfma(a[cur][i].y, b[cur][j].y, acc_i[i][j]);
-                        acc_3[i][j] = MT::mfma(as[i], bs[j], acc_3[i][j]);
-                    }
-            } else {
-                T ay[TI], by[TJ];
-#pragma unroll
-                for (int i = 0; i < TI; ++i) ay[i] = sa * a[cur][i].y;
-#pragma unroll
-                for (int j = 0; j < TJ; ++j) by[j] = sb * b[cur][j].y;
-#pragma unroll
-                for (int i = 0; i < TI; ++i)
-#pragma unroll
-                    for (int j = 0; j < TJ; ++j) {
-                        acc_r[i][j] = MT::mfma(a[cur][i].x, b[cur][j].x, acc_r[i][j]);
-                        acc_i[i][j] = MT::mfma(a[cur][i].x, by[j], acc_i[i][j]);
-                        acc_r[i][j] = MT::mfma(-ay[i], by[j], acc_r[i][j]);
-                        acc_i[i][j] = MT::mfma(ay[i], b[cur][j].x, acc_i[i][j]);
-                    }
-            }
+                for (int j = 0; j < TJ; ++j) {
+                    acc_r[i][j] = MT::mfma(a[cur][i].x, b[cur][j].x, acc_r[i][j]);
+                    acc_i[i][j] = MT::mfma(a[cur][i].y, b[cur][j].y, acc_i[i][j]);
+                    acc_3[i][j] = MT::mfma(as[i], bs[j], acc_3[i][j]);
+                }
         }
         if (more) store_tile(buf ^ 1, k0 + BK);
         __syncthreads();
@@ -270,12 +254,8 @@ __global__ void __launch_bounds__(256, 2) cgemm_kernel(int conjA, int conjB, int
             for (int r = 0; r < NR; ++r) {
                 const int64_t row = m0 + wr * WM + i * TM + MT::row_of(r, lane);
                 const int64_t col = n0 + wc * WN + j * TM + MT::col_of(lane);
-                T cr = acc_r[i][j][r], ci = acc_i[i][j][r];
-                if constexpr (M3) {
-                    const T p1 = cr, p2 = sa * sb * ci;
-                    cr = p1 - p2;
-                    ci = acc_3[i][j][r] - p1 - p2;
-                }
+                const T p1 = acc_r[i][j][r], p2 = sa * sb * acc_i[i][j][r];
+                const T cr = p1 - p2, ci = acc_3[i][j][r] - p1 - p2;
                 if (row < M && col < N) Cout[row * ldc + col] = {cr * alpha, ci * alpha};
             }
 }
@@ -340,15 +320,13 @@ struct DmaTile {
 // TI x TJ MFMA tiles (32 x 32) per wave; the four waves of a workgroup are arranged WM x WN x WK (rows, columns, K):
 //   (2, 2) tiles, 2 x 2 x 1: 128 x 128, one workgroup per CU (192 accumulator registers per lane), the large-GEMM shape;
 //   (1, 1) tiles, 2 x 2 x 1:  64 x 64;
-//   (1, 1) tiles, 2 x 1 x 2:  64 x 32, the two wave PAIRS each take half of the K range            (experiment builds: lost)
-//   (1, 1) tiles, 1 x 1 x 4:  32 x 32, every wave a quarter of the K range                         (experiment builds: no better than slabs)
 //   (1, 1) tiles, 2 x 2 x 2:  64 x 64 with EIGHT waves -- two K-groups that are each the plain 64 x 64 arrangement (same staging cost
 //                             per wave), one workgroup per CU.
 // WK > 1 is split-K INSIDE the workgroup: each K-group has its own three-deep LDS ring (A rows 32 TI WM, B rows 32 TJ WN), the groups
 // walk their K ranges in lockstep (same barriers) and their partial sums meet through LDS at the end, added in K order -- fixed
 // order, bitwise reproducible, no slab round trip through HBM and no second launch.  Shipped: the eight-wave form for outputs of 256 ..
 // 511 tiles (config 4's first product, 512 x 2048 x 2048: 108.9 us against 108.2 + 6.2 for two slabs + splitk_reduce_kernel); smaller
-// outputs (its second product, 64 tiles) keep the slabs -- the 32 x 32 four-K-group form measured equal at K = 2048 and slower at 4096.
+// outputs (its second product, 64 tiles) keep the slabs (64 x 32 and 32 x 32 tiles with the K range split over their waves measured no better: experiments/README.md).
 // EPI = 1: the epilogue stores w |alpha c|^2 into (or adds it to) a REAL matrix instead of the complex result (the incoherent sum of
 // the polychromatic recipe: focus_dft + intensity + weighted accumulate without the 512^2 complex round trip).
 template <int TI, int TJ, int WM, int WN, int WK, bool AKF, bool BKF, int EPI>
@@ -606,23 +584,16 @@ __global__ void splitk_reduce_abs2_kernel(int64_t M, int64_t N, int S, T alpha, 
     *o = accumulate ? *o + i2 : i2;
 }
 
-static int gemm_bm(int64_t M, int dtype = PM_C64) {
-    if (dtype != PM_C64) return 64;   // rows per workgroup tile: 128 (two MFMA tiles per wave along M) when M allows it
-    const int t = tuning().gemm_bm;
-    if (t == 64 || t == 128) return (t == 128 && M >= 128) ? 128 : 64;
-    return 64;
-}
-
 // plan of the LDS-DMA kernel: workgroup tile and wave arrangement, and the split of K across workgroups (slabs reduced in a fixed
-// order by splitk_reduce_kernel) only when even 32 x 32 tiles leave CUs idle
+// order by splitk_reduce_kernel) only when the 64 x 64 tiles leave CUs idle
 struct DmaPlan {
-    int tm, tn;    // workgroup tile: 128 x 128, 64 x 64 (128 x 64 measured in between: profiles/r02/exp_gemm_shapes.log), 64 x 32 or 32 x 32
-    int wk;        // K-groups inside the workgroup (1, 2 with 64 x 32, 4 with 32 x 32)
+    int tm, tn;    // workgroup tile: 128 x 128 or 64 x 64 (128 x 64 measured in between: profiles/r02/exp_gemm_shapes.log)
+    int wk;        // K-groups inside the workgroup: 1, or 2 (64 x 64 tiles with eight waves)
     int S;
     int64_t ksplit;
 };
 static bool gemm_dma_plan(int64_t M, int64_t N, int64_t K, DmaPlan* out) {
-    if (!tuning().gemm_dma || !tuning().gemm_3m || M < 64 || N < 64 || (M % 64) || (N % 64) || K < 16 || (K % 16)) return false;
+    if (!tuning().gemm_dma || M < 64 || N < 64 || (M % 64) || (N % 64) || K < 16 || (K % 16)) return false;
     DmaPlan p{64, 64, 1, 1, K};
     // workgroups the launch aims for (128 x 128 tiles from that many, else K split across workgroups until it is reached): 512 measured
     // best on config 4's products (2^31 and 2^29 multiply-adds); the 2^26 .. 2^28 products of a 1024^2 <-> 256^2 model are launch bound and
@@ -632,7 +603,7 @@ static bool gemm_dma_plan(int64_t M, int64_t N, int64_t K, DmaPlan* out) {
     if (want == 512 && M * N * K <= (int64_t(1) << 28)) want = 256;
     const bool m128 = (M % 128) == 0, n128 = (N % 128) == 0;
     const int64_t t64 = (M / 64) * (N / 64);
-    const int wkm = tuning().gemm_wk;     // bit 0: 64 x 64 with two K-groups (8 waves), bit 1: 64 x 32 with two, bit 2: 32 x 32 with four
+    const int wkm = tuning().gemm_wk;     // bit 0: 64 x 64 with two K-groups (8 waves)
     if (m128 && n128 && (M / 128) * (N / 128) >= want) p.tm = p.tn = 128;
     else if ((wkm & 1) && t64 < want && 2 * t64 >= want && (K % 32) == 0) p.wk = 2;                                  // 64 x 64, K halves
     const int t = tuning().gemm_tile;
@@ -657,7 +628,7 @@ size_t cgemm_workspace_bytes(int dtype, int64_t M, int64_t N, int64_t K, int* S_
     return a > b ? a : b;
 }
 static size_t cgemm_workspace_bytes_64(int dtype, int64_t M, int64_t N, int64_t K, int* S_out) {
-    const int BM = gemm_bm(M, dtype), BN = 64, BK = 32;   // slab depth multiple of the deepest K-tile
+    const int BM = 64, BN = 64, BK = 32;   // slab depth multiple of the deepest K-tile
     const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
     int S = 1;
     // aim for >= 2 workgroups per CU (512) while keeping >= 8 K-tiles per slab
@@ -667,10 +638,11 @@ static size_t cgemm_workspace_bytes_64(int dtype, int64_t M, int64_t N, int64_t 
     return size_t(S) * size_t(M) * size_t(N) * (dtype == PM_C64 ? 8 : 16);
 }
 
-template <typename T, int BK, int BM>
-int cgemm_ws_bm(int opA, int opB, int64_t M, int64_t N, int64_t K, double alpha, const cx<T>* A, int64_t lda,
-                const cx<T>* B, int64_t ldb, cx<T>* C, int64_t ldc, void* ws, size_t ws_bytes, hipStream_t st) {
-    constexpr int BN = 64;
+// the register-staged kernel; K-tile depth BK
+template <typename T, int BK>
+int cgemm_ws_staged(int opA, int opB, int64_t M, int64_t N, int64_t K, double alpha, const cx<T>* A, int64_t lda,
+                    const cx<T>* B, int64_t ldb, cx<T>* C, int64_t ldc, void* ws, size_t ws_bytes, hipStream_t st) {
+    constexpr int BM = 64, BN = 64;
     int S = 1;
     const size_t need = cgemm_workspace_bytes_64(sizeof(T) == 4 ? PM_C64 : PM_C128, M, N, K, &S);
     if (S > 1 && (!ws || ws_bytes < need)) S = 1;   // no workspace: fall back to unsplit (still correct)
@@ -685,17 +657,12 @@ int cgemm_ws_bm(int opA, int opB, int64_t M, int64_t N, int64_t K, double alpha,
     const int cA = opA & 1, cB = opB & 1;
     auto launch = [&](T al, cx<T>* out, int64_t ldo, int64_t slab) {
         constexpr size_t LDSB = sizeof(cx<T>) * 2 * BK * ((BM + 1) + (BN + 1));
-#define PM_GEMM_(AK, BK_, M3_)                                                                                             \
+#define PM_GEMM(AK, BK_)                                                                                                   \
     {                                                                                                                      \
-        auto kern = cgemm_kernel<T, BM, BN, BK, AK, BK_, M3_>;                                                             \
+        auto kern = cgemm_kernel<T, BK, AK, BK_>;                                                                          \
         if (LDSB > 48 * 1024)                                                                                              \
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(LDSB)); \
         hipLaunchKernelGGL(kern, grid, dim3(256), LDSB, st, cA, cB, M, N, K, ksplit, al, A, lda, B, ldb, out, ldo, slab);  \
-    }
-#define PM_GEMM_3M_OR_4(AK, BK_) PM_GEMM_(AK, BK_, true)
-#define PM_GEMM(AK, BK_)                     \
-    {                                        \
-        PM_GEMM_3M_OR_4(AK, BK_)             \
     }
         if (akf && bkf) {
             PM_GEMM(true, true)
@@ -707,8 +674,6 @@ int cgemm_ws_bm(int opA, int opB, int64_t M, int64_t N, int64_t K, double alpha,
             PM_GEMM(false, false)
         }
 #undef PM_GEMM
-#undef PM_GEMM_3M_OR_4
-#undef PM_GEMM_
     };
     if (S == 1) {
         launch(T(alpha), C, ldc, int64_t(0));
@@ -722,12 +687,6 @@ int cgemm_ws_bm(int opA, int opB, int64_t M, int64_t N, int64_t K, double alpha,
     hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, M, N, S, T(alpha),
                        slabs, M * N, C, ldc);
     return int(hipGetLastError());
-}
-
-template <typename T, int BK>
-int cgemm_ws_bk(int opA, int opB, int64_t M, int64_t N, int64_t K, double alpha, const cx<T>* A, int64_t lda,
-                const cx<T>* B, int64_t ldb, cx<T>* C, int64_t ldc, void* ws, size_t ws_bytes, hipStream_t st) {
-    return cgemm_ws_bm<T, BK, 64>(opA, opB, M, N, K, alpha, A, lda, B, ldb, C, ldc, ws, ws_bytes, st);
 }
 
 struct DmaEpi {
@@ -803,10 +762,9 @@ int cgemm_ws(int opA, int opB, int64_t M, int64_t N, int64_t K, double alpha, co
             reinterpret_cast<uintptr_t>(B) % 16 == 0)
             return cgemm_dma_run(opA, opB, M, N, K, alpha, A, lda, B, ldb, C, ldc, ws, ws_bytes, st, dp);
     }
-    // K-tile depth: 16 (fp32) / 8 (fp64) = 33 KiB of LDS, 4 workgroups per CU; tuning gemm_bk = 32 / 16 doubles it
-    // (66.5 KiB, 2 per CU, half the barriers per flop)
-    if (sizeof(T) == 4) return cgemm_ws_bk<T, 16>(opA, opB, M, N, K, alpha, A, lda, B, ldb, C, ldc, ws, ws_bytes, st);
-    return cgemm_ws_bk<T, 8>(opA, opB, M, N, K, alpha, A, lda, B, ldb, C, ldc, ws, ws_bytes, st);
+    // K-tile depth: 16 (fp32) / 8 (fp64) = 33 KiB of LDS, 4 workgroups per CU
+    if (sizeof(T) == 4) return cgemm_ws_staged<T, 16>(opA, opB, M, N, K, alpha, A, lda, B, ldb, C, ldc, ws, ws_bytes, st);
+    return cgemm_ws_staged<T, 8>(opA, opB, M, N, K, alpha, A, lda, B, ldb, C, ldc, ws, ws_bytes, st);
 }
 
 }  // namespace pm

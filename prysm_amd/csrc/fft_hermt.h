@@ -353,7 +353,7 @@ int launch_row_hermt_one(const RowLoadNat<T>& lp, const HermTRowStore<T>& sp, co
     }
 }
 
-// one tiling per length and precision, the complex path's (pm_internal.h row_variant): `var` only tells 4096-point complex64 rows apart;
+// one tiling per length and precision, the complex path's (fft_kernels.h built_row_var): `var` (Fft2Plan::hermt_row_var) only tells 4096-point complex64 rows apart;
 // which lengths have a kernel is hermt_row_kernel's alone
 template <typename T>
 int launch_row_hermt_impl(int logn, int var, const RowLoadNat<T>& lp, const HermTRowStore<T>& sp, const cx<T>* tw, int log_g, hipStream_t st) {

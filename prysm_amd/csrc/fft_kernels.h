@@ -14,7 +14,7 @@ constexpr int kMaxLogN = 13;  // 8192: the largest length one workgroup holds on
 // ---- per-length configurations -------------------------------------------------------------
 // Row pass: one sequence per N/16 threads, 256 threads per workgroup (512 at N = 8192); LDS is
 // 8.5 B per point (complex64) so 4 workgroups / CU stay resident at N = 4096.
-// VAR (row_variant() in pm_internal.h picks it per length / precision):
+// VAR (built_row_var() below picks it per length / precision):
 //   1: real and imaginary parts exchanged separately -> half the LDS per workgroup (complex128 rows of 2048 points)
 //   4: two rows per thread -- stage twiddles, their products and the LDS addressing are shared by the pair (complex64 from
 //      4096 points; the folded row pass pairs rows (i, i + M/2) this way)
@@ -455,12 +455,15 @@ int launch_unfold_impl(int logn, const RowLoadFold<T>& lp, const RowStoreNat<T>&
     }
 }
 
-// The row-pass tiling per length and precision (what pm_internal.h row_variant() returns; measured in rounds 1 - 2): only THAT one is
-// built.  Until round 5 every length from 2048 points carried all four tilings of both precisions for the knob row_var -- 12 dead
-// kernel families per loader / storer pair, 7 MB of the library.
+// The row-pass tiling per length and precision (measured on MI355X in rounds 1 - 2, profiles/r01/sweep*.log): only THAT one is built,
+// and this is the one place that states it.  Until round 5 every length from 2048 points carried all four tilings of both precisions
+// behind a knob -- 12 dead kernel families per loader / storer pair, 7 MB of the library.
 template <typename T, int LOGN>
 constexpr int built_row_var() {
+    // complex64: two rows per thread (4) from 4096 points: 53.5 -> 51.4 us at 4096^2, 226 -> 207 us at 8192^2 (it loses for complex128:
+    // register pressure); at 2048 points one row per 128-thread workgroup (5): twice the workgroups, 17.9 -> 16.5 us at 2048^2
     if (sizeof(T) == 4) return LOGN >= 12 ? 4 : (LOGN == 11 ? 5 : 0);
+    // complex128: the half-LDS exchange (1) at 2048 points: 24.3 against 28.3 us
     return LOGN == 11 ? 1 : 0;
 }
 
@@ -470,8 +473,8 @@ int launch_fft(int logn, int var, const L& lp, const S& sp, const cx<T>* tw, int
 #define PM_CASE(k) \
     case k:        \
         return launch_one<T, COL, k, 0, L, S>(lp, sp, tw, units, log_g, st, nbatch);
-// lengths with more than one tiling (see RowCfgSel / ColCfgSel): rows take the built one; columns the 128 B tiles (var 2) for
-// 2048-point complex128 tiles, else the 64 B tiles
+// lengths with more than one tiling (see RowCfgSel / ColCfgSel): rows take the built one (`var` is the column pass's alone); columns the
+// 128 B tiles (var 2) for 2048-point complex128 tiles, else the 64 B tiles
 #define PM_CASEV(k)                                                                                              \
     case k:                                                                                                      \
         if constexpr (!COL) return launch_one<T, COL, k, (COL ? 0 : built_row_var<T, k>()), L, S>(lp, sp, tw, units, log_g, st, nbatch); \
@@ -489,16 +492,16 @@ int launch_fft(int logn, int var, const L& lp, const S& sp, const cx<T>* tw, int
 }
 
 // entry points, one explicit instantiation per .hip file
-template <typename T> int launch_row_tiled(int logn, int var, const RowLoadNat<T>&, const RowStoreTiled<T>&, const cx<T>* tw, int nseq, int log_g, hipStream_t, int nbatch = 1);
-template <typename T> int launch_row_nat(int logn, int var, const RowLoadNat<T>&, const RowStoreNat<T>&, const cx<T>* tw, int nseq, int log_g, hipStream_t, int nbatch = 1);
+template <typename T> int launch_row_tiled(int logn, const RowLoadNat<T>&, const RowStoreTiled<T>&, const cx<T>* tw, int nseq, int log_g, hipStream_t, int nbatch = 1);
+template <typename T> int launch_row_nat(int logn, const RowLoadNat<T>&, const RowStoreNat<T>&, const cx<T>* tw, int nseq, int log_g, hipStream_t, int nbatch = 1);
 template <typename T> int launch_col_tiled(int logm, int var, const ColLoadTiled<T>&, const ColStoreNat<T>&, const cx<T>* tw, int ntiles, int log_g, hipStream_t, int nbatch = 1);
 template <typename T> int launch_col_nat(int logm, int var, const ColLoadNat<T>&, const ColStoreNat<T>&, const cx<T>* tw, int ntiles, int log_g, hipStream_t, int nbatch = 1);
 template <typename T> int launch_col_mul(int logm, const ColLoadTiled<T>&, const MidMul<T>&, const ColStoreTiled<T>&, const cx<T>* tw, int ntiles, int log_g, hipStream_t, int nbatch = 1, int mode = 0);
 template <typename T> int launch_col_mul_crop(int logm, const ColLoadTiled<T>&, const MidMul<T>&, const ColStoreTiledCrop<T>&, const cx<T>* tw, int ntiles, int log_g, hipStream_t);
-template <typename T> int launch_row_from_tiled(int logn, int var, const RowLoadTiled<T>&, const RowStoreNat<T>&, const cx<T>* tw, int nseq, hipStream_t, int nbatch = 1);
+template <typename T> int launch_row_from_tiled(int logn, const RowLoadTiled<T>&, const RowStoreNat<T>&, const cx<T>* tw, int nseq, hipStream_t, int nbatch = 1);
 template <typename T> int launch_row_fold(int logn, const RowLoadNat<T>&, const RowStoreFold<T>&, const cx<T>* tw, int npairs, int log_g, hipStream_t, int nbatch = 1);
 template <typename T> int launch_row_unfold(int logn, const RowLoadFold<T>&, const RowStoreNat<T>&, const cx<T>* tw, int npairs, hipStream_t, int nbatch = 1);
-template <typename T> int launch_row_chirp_tiled(int logn, int var, const RowLoadChirp<T>&, const RowStoreTiled<T>&, const cx<T>* tw, int nseq, int log_g, hipStream_t);
-template <typename T> int launch_row_tiled_chirp(int logn, int var, const RowLoadTiled<T>&, const RowStoreChirp<T>&, const cx<T>* tw, int nseq, hipStream_t);
+template <typename T> int launch_row_chirp_tiled(int logn, const RowLoadChirp<T>&, const RowStoreTiled<T>&, const cx<T>* tw, int nseq, int log_g, hipStream_t);
+template <typename T> int launch_row_tiled_chirp(int logn, const RowLoadTiled<T>&, const RowStoreChirp<T>&, const cx<T>* tw, int nseq, hipStream_t);
 
 }  // namespace pm

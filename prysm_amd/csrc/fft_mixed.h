@@ -204,9 +204,7 @@ struct MixShape {
     // 512 cycles by a hash of their index, so that the load / butterfly / store phases of the workgroups of a CU -- which otherwise
     // start together and stay in step -- overlap
     int stagger, first_round;
-    int pers_tiles;     // > 0: the persistent column kernel (fft_mixed_kernels.h mix_cols_pers_kernel) over this many tiles
 };
-#define PM_MIX_ABLATE(sh, bit) false
 inline void mix_shape_pads(const MixPlan& p, MixShape& sh, int c0, int c1);
 
 // floor(a / d) for a d < 2^16 as (a * magic) >> 32, magic = floor(2^32 / d) + 1 (exact while a d < 2^32); d == 1: magic 0 = identity
@@ -428,9 +426,9 @@ PM_HD void mix_first(const MixPlan& p, MixShape sh, int tid, int nt, cx<T>* lds,
             sl[u] = j[u] = 0;
             if (b0 + u * nt < total) {
                 mix_split<COL>(sh, b0 + u * nt, mg_nb0, nb, sl[u], j[u]);
-                wr[u] = MixTw<T, R>::load(tw, PM_MIX_ABLATE(sh, 2) ? 0u : uint32_t(j[u]));
+                wr[u] = MixTw<T, R>::load(tw, uint32_t(j[u]));
 #pragma unroll
-                for (int k = 0; k < R; ++k) a[u][k] = PM_MIX_ABLATE(sh, 1) ? cx<T>{T(j[u] + k), T(sl[u])} : fetch(sl[u], j[u] + k * nb);
+                for (int k = 0; k < R; ++k) a[u][k] = fetch(sl[u], j[u] + k * nb);
             }
         }
 #pragma unroll
@@ -438,7 +436,7 @@ PM_HD void mix_first(const MixPlan& p, MixShape sh, int tid, int nt, cx<T>* lds,
             if (b0 + u * nt < total) {
 #pragma unroll
                 for (int k = 0; k < R; ++k) a[u][k] = mix_finish(fetch, a[u][k], 0);
-                if (!PM_MIX_ABLATE(sh, 8)) MixDft<T, R>::run(a[u]);
+                MixDft<T, R>::run(a[u]);
                 const int a0 = mix_addr<COL>(n, sh, sl[u], mix_slot_low(p, sh, j[u])), as = mix_step<COL>(sh, sh.s0);
                 mix_st(lds + a0, a[u][0]);
                 const MixTw<T, R> w(wr[u]);
@@ -447,36 +445,6 @@ PM_HD void mix_first(const MixPlan& p, MixShape sh, int tid, int nt, cx<T>* lds,
             }
         }
     }
-}
-
-// first stage on a sequence that is already in LDS at its slots (the persistent column kernel copies the tile in): point j + k nb sits
-// in slot slot_low(j) + k s0, which is also where the stage leaves digit k -- in place, like a middle stage
-template <typename T, bool COL, int R>
-PM_HD void mix_first_lds(const MixPlan& p, MixShape sh, int tid, int nt, cx<T>* lds, const cx<T>* __restrict__ tw) {
-    const int n = p.n, nb = p.len[1], total = sh.seqs * nb;
-    const uint32_t mg_nb0 = p.mg_nb[0];
-#pragma unroll 1
-    for (int b = tid; b < total; b += nt) {
-        int sl, j;
-        mix_split<COL>(sh, b, mg_nb0, nb, sl, j);
-        const typename MixTw<T, R>::Raw wr = MixTw<T, R>::load(tw, uint32_t(j));
-        const int a0 = mix_addr<COL>(n, sh, sl, mix_slot_low(p, sh, j)), as = mix_step<COL>(sh, sh.s0);
-        cx<T> a[R];
-#pragma unroll
-        for (int k = 0; k < R; ++k) a[k] = mix_ld(lds + a0 + k * as);
-        MixDft<T, R>::run(a);
-        mix_st(lds + a0, a[0]);
-        const MixTw<T, R> w(wr);
-#pragma unroll
-        for (int k = 1; k < R; ++k) mix_st(lds + a0 + k * as, cmul(a[k], w(k)));
-    }
-}
-// LDS slot of point i of a sequence (any i < n): the copy-in of the persistent column kernel
-PM_HD int mix_slot_of(const MixPlan& p, MixShape sh, int i) {
-    int r = i;
-    if (sh.pad1) r += int(mix_mul24(uint32_t(sh.pad1), uint32_t(mix_div(i, p.mg_sub[1]))));
-    if (sh.pad0) r += int(mix_mul24(uint32_t(sh.pad0), uint32_t(mix_div(i, p.mg_sub[0]))));
-    return r;
 }
 
 // middle stage s: LDS in place
@@ -490,11 +458,11 @@ PM_HD void mix_mid(const MixPlan& p, MixShape sh, int s, int tid, int nt, cx<T>*
         mix_split<COL>(sh, b, mg_nb, nb, sl, ja);
         const int blk = mix_div(ja, mg_sub), j = ja - int(mix_mul24(uint32_t(blk), uint32_t(sub)));
         const int a0 = mix_addr<COL>(n, sh, sl, mix_slot_mid(p, sh, s, blk, j, L)), as = mix_step<COL>(sh, s == 1 ? sh.s1 : sub);
-        const typename MixTw<T, R>::Raw wr = MixTw<T, R>::load(tw, PM_MIX_ABLATE(sh, 2) ? 0u : mix_mul24(uint32_t(j), uint32_t(tstep)));
+        const typename MixTw<T, R>::Raw wr = MixTw<T, R>::load(tw, mix_mul24(uint32_t(j), uint32_t(tstep)));
         cx<T> a[R];
 #pragma unroll
         for (int k = 0; k < R; ++k) a[k] = mix_ld(lds + a0 + k * as);
-        if (!PM_MIX_ABLATE(sh, 8)) MixDft<T, R>::run(a);
+        MixDft<T, R>::run(a);
         mix_st(lds + a0, a[0]);
         const MixTw<T, R> w(wr);
 #pragma unroll
@@ -533,10 +501,9 @@ PM_HD void mix_last(const MixPlan& p, MixShape sh, int tid, int nt, const cx<T>*
         cx<T> a[R];
 #pragma unroll
         for (int k = 0; k < R; ++k) a[k] = mix_ld(lds + a0 + k * as);
-        if (!PM_MIX_ABLATE(sh, 8)) MixDft<T, R>::run(a);
+        MixDft<T, R>::run(a);
 #pragma unroll
-        for (int k = 0; k < R; ++k)
-            if (!PM_MIX_ABLATE(sh, 4) || a[k].x == T(-12345.678)) store(sl, o + k * nb, a[k]);
+        for (int k = 0; k < R; ++k) store(sl, o + k * nb, a[k]);
     }
 }
 
@@ -665,14 +632,6 @@ struct MixRowOut {
     T scale;
     int conj;
     int mapped;
-    // FOLD (round 4, experiment builds: it measured SLOWER than the unfolded pair of passes -- 3000^2 complex64 78.9 -> 87.7 us, 4000^2 126 -> 143,
-    // complex128 3000^2 175 -> 199, profiles/r04/exp_mix_fold.log: two rows per workgroup cost the row pass more than the half-height tiles give
-    // the column pass; the engine's RowStoreFold on composite lengths): the workgroup's two rows are (g, g + fold_h) of an array of 2 fold_h
-    // rows, and what is stored is one radix-2 decimation-in-frequency step of the COLUMN transform -- plane 0 row g = y[g] + y[g + H],
-    // plane 1 row g = (y[g] - y[g + H]) W_M^g (planes fold_h rows apart); the column pass then runs H-point tiles, half the LDS each.
-    // fold_tw[g] = W_M^g; fold_swap: the input rows are rotated by H, so the two rows of the pair trade places (plane 1 changes sign)
-    int fold_h, fold_swap;
-    const cx<T>* fold_tw;
 };
 
 template <typename T>
@@ -693,10 +652,6 @@ PM_HD void mix_store_row(const MixRowOut<T>& o, int seq, int k, cx<T> v) {
 template <typename T, bool COL, int MAXR, int UCAP = 1, typename Fetch>
 PM_HD void mix_run_first(const MixPlan& p, MixShape sh, int tid, int nt, cx<T>* lds, const cx<T>* __restrict__ tw, Fetch fetch) {
     PM_MIX_RADIX_SWITCH(p.radix[0], (mix_first<T, COL, R, UCAP>(p, sh, tid, nt, lds, tw, fetch)))
-}
-template <typename T, bool COL, int MAXR>
-PM_HD void mix_run_first_lds(const MixPlan& p, MixShape sh, int tid, int nt, cx<T>* lds, const cx<T>* __restrict__ tw) {
-    PM_MIX_RADIX_SWITCH(p.radix[0], (mix_first_lds<T, COL, R>(p, sh, tid, nt, lds, tw)))
 }
 template <typename T, bool COL, int MAXR>
 PM_HD void mix_run_mid(const MixPlan& p, MixShape sh, int s, int tid, int nt, cx<T>* lds, const cx<T>* __restrict__ tw) {

@@ -83,11 +83,10 @@ __global__ __launch_bounds__(512) void mix_rows_kernel(const MixPlan* __restrict
     const MixPlan& p = *pp;
     extern __shared__ __align__(16) char mix_smem[];
     cx<T>* lds = reinterpret_cast<cx<T>*>(mix_smem);
-    // the rows of the workgroup: seqs consecutive ones, or (FOLD, experiment builds) the pair (g, g + H)
-    constexpr bool fold = false;
-    const int seq0 = fold ? int(blockIdx.x) : int(blockIdx.x) * sh.seqs, tid = threadIdx.x, nt = blockDim.x;
-    const int nvalid = fold ? 2 : (in.nseq - seq0 < sh.seqs ? in.nseq - seq0 : sh.seqs);
-    const uint32_t rpitch = fold ? uint32_t(out.fold_h) * uint32_t(in.s_seq) : uint32_t(in.s_seq);
+    // the rows of the workgroup: seqs consecutive ones
+    const int seq0 = int(blockIdx.x) * sh.seqs, tid = threadIdx.x, nt = blockDim.x;
+    const int nvalid = in.nseq - seq0 < sh.seqs ? in.nseq - seq0 : sh.seqs;
+    const uint32_t rpitch = uint32_t(in.s_seq);
     const T ysign = in.conj ? T(-1) : T(1);
     const bool whole = in.ax.off == 0 && in.ax.len == in.ax.n && nvalid == sh.seqs;
     if (SYNTH && in.synth == 3) {
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(512) void mix_rows_kernel(const MixPlan* __restrict
         const char* a0 = reinterpret_cast<const char*>(in.amp);
         if (a0) a0 += int64_t(seq0) * in.amp_ld * (in.amp_kind == 1 ? 4 : (in.amp_kind == 2 ? 8 : 1));
         const MixFetchSynth<T, false> fetch{reinterpret_cast<const T*>(in.src) + int64_t(seq0) * in.s_seq, rpitch, in.ax, nvalid, in.k2,
-                                            a0, a0 ? in.amp_kind : 0, fold ? uint32_t(out.fold_h) * uint32_t(in.amp_ld) : uint32_t(in.amp_ld)};
+                                            a0, a0 ? in.amp_kind : 0, uint32_t(in.amp_ld)};
         mix_run_first<T, true, MAXR>(p, sh, tid, nt, lds, tw, fetch);
     } else if (in.real) {
         const MixFetch<T, false, true> fetch{reinterpret_cast<const T*>(in.src) + int64_t(seq0) * in.s_seq, rpitch, in.ax, ysign, nvalid};
@@ -177,8 +176,6 @@ __global__ __launch_bounds__(NTMAX) void mix_cols_kernel(const MixPlan* __restri
         mix_run_last<T, true, MAXR>(p, sh, tid, nt, lds, store);
     }
 }
-
-
 
 // Middle pass of fft2 -> x H -> ifft2 on a composite column length (fft_mixed.h, the transposed stages): a tile of adjacent columns of the
 // natural intermediate goes through forward stages, the multiplier and the transposed stages without leaving the LDS, and comes back as
@@ -337,27 +334,24 @@ int mix_cols_launch_impl(const MixPlan* p, MixShape sh, const DirectIn<T>& in, c
 }
 
 template <typename T>
-int mix_rows_impl(const DirectIn<T>& in, cx<T>* out, int64_t out_ld, hipStream_t st, const RowStoreNat<T>* o, const MixFold<T>* fold, int64_t out_bstride) {
+int mix_rows_impl(const DirectIn<T>& in, cx<T>* out, int64_t out_ld, hipStream_t st, const RowStoreNat<T>* o, int64_t out_bstride) {
     const int n = in.ax.n, nseq = in.nseq;
     if (nseq <= 0 || n <= 0) return 0;
-    if (!fold && tuning().mix_engine) {     // a length with a compile-time plan, a plain view: the register engine (fft_ce.h)
+    if (tuning().mix_engine) {     // a length with a compile-time plan, a plain view: the register engine (fft_ce.h)
         int rc = 0;
         if (ce_rows<T>(in, out, out_ld, o, st, &rc, out_bstride)) return rc;
     }
     if (in.nb > 1) {      // a stack on the general kernel: field by field (complex fields, natural outputs: capi.hip fft2_run)
-        if (o || fold || in.real || in.synth) return fail(PM_ERR_UNSUPPORTED, "mixed-radix path: a stack with a view it does not take");
+        if (o || in.real || in.synth) return fail(PM_ERR_UNSUPPORTED, "mixed-radix path: a stack with a view it does not take");
         for (int b = 0; b < in.nb; ++b) {
             DirectIn<T> one = in;
             one.src = in.src + int64_t(b) * in.bstride;
             one.nb = 1;
-            const int rc = mix_rows_impl<T>(one, out + int64_t(b) * out_bstride, out_ld, st, nullptr, nullptr, 0);
+            const int rc = mix_rows_impl<T>(one, out + int64_t(b) * out_bstride, out_ld, st, nullptr, 0);
             if (rc) return rc;
         }
         return 0;
     }
-    if (fold && (o || nseq != 2 * fold->H || !mix_fits(n, int64_t(fold->H) * in.s_seq, sizeof(cx<T>), false) ||
-                 (in.amp && !mix_fits(n, int64_t(fold->H) * in.amp_ld, sizeof(cx<T>), false))))
-        return fail(PM_ERR_UNSUPPORTED, "mixed-radix path: folded row pass on a shape it does not take");
     MixPlan p;
     if (!mix_plan_for(n, sizeof(cx<T>), p)) return fail(PM_ERR_UNSUPPORTED, "mixed-radix path: length %d has no plan", n);
     if (in.s_i != 1 || !mix_fits(n, in.s_seq, sizeof(cx<T>), false) || !mix_fits(n, o ? o->ld : out_ld, sizeof(cx<T>), false))
@@ -376,7 +370,6 @@ int mix_rows_impl(const DirectIn<T>& in, cx<T>* out, int64_t out_ld, hipStream_t
     while (seqs > 1 && size_t(seqs) * per > size_t(48) * 1024) --seqs;
     if (tuning().mix_seqs > 0) seqs = tuning().mix_seqs;
     while (seqs > 1 && seqs / 2 >= nseq) seqs /= 2;
-    if (fold) seqs = 2;
     {   // a power of two: the rows of a workgroup are interleaved in LDS (mix_rows_kernel)
         int pw = 1;
         while (pw * 2 <= seqs) pw *= 2;
@@ -390,14 +383,9 @@ int mix_rows_impl(const DirectIn<T>& in, cx<T>* out, int64_t out_ld, hipStream_t
     const MixPlan* pd = mix_plan_dev(n, sizeof(cx<T>), &err);
     if (!pd) return err;
     const size_t lds = size_t(seqs) * size_t(sh.npad) * sizeof(cx<T>);
-    MixRowOut<T> ro{out, out_ld, AxisMap{n, n, 0, 0}, T(1), 0, 0, 0, 0, nullptr};
-    if (o) ro = MixRowOut<T>{o->dst, o->ld, o->ax, o->scale, o->conj, 1, 0, 0, nullptr};
-    if (fold) {
-        ro.fold_h = fold->H;
-        ro.fold_swap = fold->swap;
-        ro.fold_tw = fold->tw;
-    }
-    const int groups = fold ? fold->H : (nseq + seqs - 1) / seqs, nt = mix_threads(p, seqs, 256, tuning().mix_nt, false);
+    MixRowOut<T> ro{out, out_ld, AxisMap{n, n, 0, 0}, T(1), 0, 0};
+    if (o) ro = MixRowOut<T>{o->dst, o->ld, o->ax, o->scale, o->conj, 1};
+    const int groups = (nseq + seqs - 1) / seqs, nt = mix_threads(p, seqs, 256, tuning().mix_nt, false);
     sh.stagger = 0;
     if (p.maxr <= 10) return mix_rows_launch<T, 10>(pd, sh, in, ro, tw, groups, nt, lds, st);
     if (p.maxr <= 16) return mix_rows_launch<T, 16>(pd, sh, in, ro, tw, groups, nt, lds, st);
@@ -477,10 +465,6 @@ int mix_cols_impl(const DirectIn<T>& in, const ColStoreNat<T>& out, hipStream_t 
     // at 0 / 4 / 8 units (profiles/r04/exp_mix_stagger.log): complex64 3000^2 75.4 / 74.3 / 76.6, 4000^2 131.2 / 129.7 / 127.6, complex128
     // 3000^2 167.1 / 166.4 / 160.8, 2000^2 62.7 / 59.6 / 65.3; a single round only pays the delay (complex64 2000^2 35.6 / 38.3 / 43.6)
     if (lds <= size_t(80) * 1024 || tiles <= sh.first_round) sh.stagger = 0;
-    // persistent workgroups (mix_cols_pers_kernel) where a CU holds one tile: more tiles than CUs, whole tiles, a plain complex input
-    const bool whole_in = !in.real && in.ax.off == 0 && in.ax.len == in.ax.n, whole_out = out.ay.off == 0 && out.ay.len == out.ay.n && out.ax.off == 0 && out.ax.len == out.ax.n;
-    const bool aligned = (reinterpret_cast<uintptr_t>(in.src) & 15) == 0 && ((size_t(in.s_i) * sizeof(cx<T>)) & 15) == 0 && size_t(tc) * sizeof(cx<T>) >= 16;
-    if (tuning().mix_pers && lds > size_t(80) * 1024 && lds <= size_t(128) * 1024 && tiles > 256 && ncols % tc == 0 && whole_in && whole_out && aligned && out.bstride == 0) sh.pers_tiles = tiles;
     if (p.maxr <= 10) return mix_cols_launch<T, 10>(pd, sh, in, out, tw, log_g, groups, nt, lds, st);
     if (p.maxr <= 16) return mix_cols_launch<T, 16>(pd, sh, in, out, tw, log_g, groups, nt, lds, st);
     return mix_cols_launch<T, 20>(pd, sh, in, out, tw, log_g, groups, nt, lds, st);

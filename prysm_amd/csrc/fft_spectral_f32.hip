@@ -3,7 +3,7 @@
 namespace pm {
 
 template <>
-int launch_row_spectral<float>(int logn, int var, const RowLoadNat<float>& l, const RowStoreTiled<float>& s, const cx<float>* tw, int nseq,
+int launch_row_spectral<float>(int logn, const RowLoadNat<float>& l, const RowStoreTiled<float>& s, const cx<float>* tw, int nseq,
                                int log_g, const Spectral& w, hipStream_t st) {
     using T = float;
     using S = RowStoreTiled<T>;
@@ -13,10 +13,8 @@ int launch_row_spectral<float>(int logn, int var, const RowLoadNat<float>& l, co
         return launch_row_spectral_one<T, k, 0, S>(l, s, tw, nseq, log_g, w, st);
         PM_CASE(5) PM_CASE(6) PM_CASE(7) PM_CASE(8) PM_CASE(9) PM_CASE(10)
 #undef PM_CASE
-        case 11: return var == 5 ? launch_row_spectral_one<T, 11, 5, S>(l, s, tw, nseq, log_g, w, st)
-                                 : launch_row_spectral_one<T, 11, 0, S>(l, s, tw, nseq, log_g, w, st);
-        case 12: return var == 4 ? launch_row_spectral_one<T, 12, 4, S>(l, s, tw, nseq, log_g, w, st)
-                                 : launch_row_spectral_one<T, 12, 0, S>(l, s, tw, nseq, log_g, w, st);
+        case 11: return launch_row_spectral_one<T, 11, built_row_var<T, 11>(), S>(l, s, tw, nseq, log_g, w, st);
+        case 12: return launch_row_spectral_one<T, 12, built_row_var<T, 12>(), S>(l, s, tw, nseq, log_g, w, st);
         default: return -2;     // 8192-point rows take the per-wavelength loop (capi.hip spectral_fast): this kernel spilled there
     }
 }

@@ -4,7 +4,7 @@
 namespace pm {
 
 template <>
-int launch_row_spectral<double>(int logn, int var, const RowLoadNat<double>& l, const RowStoreTiled<double>& s, const cx<double>* tw, int nseq,
+int launch_row_spectral<double>(int logn, const RowLoadNat<double>& l, const RowStoreTiled<double>& s, const cx<double>* tw, int nseq,
                                 int log_g, const Spectral& w, hipStream_t st) {
     using T = double;
     using S = RowStoreTiled<T>;
@@ -14,8 +14,7 @@ int launch_row_spectral<double>(int logn, int var, const RowLoadNat<double>& l, 
         return launch_row_spectral_one<T, k, 0, S>(l, s, tw, nseq, log_g, w, st);
         PM_CASE(5) PM_CASE(6) PM_CASE(7) PM_CASE(8) PM_CASE(9) PM_CASE(10)
 #undef PM_CASE
-        case 11: return var == 1 ? launch_row_spectral_one<T, 11, 1, S>(l, s, tw, nseq, log_g, w, st)
-                                 : launch_row_spectral_one<T, 11, 0, S>(l, s, tw, nseq, log_g, w, st);
+        case 11: return launch_row_spectral_one<T, 11, built_row_var<T, 11>(), S>(l, s, tw, nseq, log_g, w, st);
         default: return -2;
     }
 }

@@ -11,12 +11,11 @@ struct Spectral {
     double w[kSpectralMax];     // spectral weights
     double k2[kSpectralMax];    // phase in turns per OPD unit: k / (2 pi), per wavelength
     int64_t fstride;            // elements between the intermediates of consecutive wavelengths
-    int mode;                   // bit 0: rows keep the packed map in registers; bit 1: columns accumulate in registers (fft_spectral.h)
 };
 
-// rows: VAR as launch_row_tiled; the store's bstride must be sp.fstride
+// rows: the tiling of launch_row_tiled (fft_kernels.h built_row_var); the store's bstride must be sp.fstride
 template <typename T>
-int launch_row_spectral(int logn, int var, const RowLoadNat<T>&, const RowStoreTiled<T>&, const cx<T>* tw, int nseq, int log_g, const Spectral&,
+int launch_row_spectral(int logn, const RowLoadNat<T>&, const RowStoreTiled<T>&, const cx<T>* tw, int nseq, int log_g, const Spectral&,
                         hipStream_t);
 template <typename T>
 int launch_row_spectral_fold(int logn, const RowLoadNat<T>&, const RowStoreFold<T>&, const cx<T>* tw, int npairs, const Spectral&, hipStream_t);

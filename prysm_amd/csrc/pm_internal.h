@@ -65,16 +65,8 @@ int blue_cols(const DirectIn<T>& in, const ColStoreNat<T>& out, void* scratch, h
 
 // Mixed-radix path (fft_mixed.hip): lengths up to 8192 whose prime factors are all <= 19 (<= 13 until round 4), one kernel per axis with the data in LDS, no
 // scratch.  Same contracts as direct_rows / direct_rows_out (`o`) / direct_cols.
-// `fold` (round 4): the rows are taken in pairs (g, g + H) of an array of 2 H rows and the intermediate holds one radix-2 step of the
-// column transform (two planes of H rows, fft_mixed.h MixRowOut): tw = the device table of W_M^g (M = 2 H), swap = rows rotated by H
 template <typename T>
-struct MixFold {
-    int H, swap;
-    const cx<T>* tw;
-};
-template <typename T>
-int mix_rows(const DirectIn<T>& in, cx<T>* out, int64_t out_ld, hipStream_t st, const RowStoreNat<T>* o = nullptr, const MixFold<T>* fold = nullptr,
-             int64_t out_bstride = 0);      // out_bstride: elements between the natural outputs of the fields of a stack (in.nb > 1)
+int mix_rows(const DirectIn<T>& in, cx<T>* out, int64_t out_ld, hipStream_t st, const RowStoreNat<T>* o = nullptr, int64_t out_bstride = 0);      // out_bstride: elements between the natural outputs of the fields of a stack (in.nb > 1)
 template <typename T>
 int mix_cols(const DirectIn<T>& in, const ColStoreNat<T>& out, hipStream_t st);
 // the composite register engine (fft_ce.h): lengths with a compile-time plan, plain views.  false: not taken (the general kernel runs);
@@ -98,23 +90,23 @@ template <typename T>
 int blue_post2d(const cx<T>* t, int n1, int n2, const cx<T>* w1, const cx<T>* w2, const ColStoreNat<T>& out, hipStream_t st);
 
 // the same chain with the chirp multiplies riding on its first load and its last store (fft_row_*.hip instantiations)
-template <typename T> int launch_row_chirp_tiled(int logn, int var, const RowLoadChirp<T>&, const RowStoreTiled<T>&, const cx<T>* tw, int nseq, int log_g, hipStream_t);
-template <typename T> int launch_row_tiled_chirp(int logn, int var, const RowLoadTiled<T>&, const RowStoreChirp<T>&, const cx<T>* tw, int nseq, hipStream_t);
+template <typename T> int launch_row_chirp_tiled(int logn, const RowLoadChirp<T>&, const RowStoreTiled<T>&, const cx<T>* tw, int nseq, int log_g, hipStream_t);
+template <typename T> int launch_row_tiled_chirp(int logn, const RowLoadTiled<T>&, const RowStoreChirp<T>&, const cx<T>* tw, int nseq, hipStream_t);
 
 // power-of-two lengths above the engine's longest transform (bigfft.hip; orchestration: capi.hip big2d_run)
 template <typename T> int big_pre_rows(const Blue2dIn<T>& in, int M, int np, int R, cx<T>* Y, const cx<T>* twN, hipStream_t st);
 template <typename T>
 int big_finish(const cx<T>* F, int mp, int np, int Rm, int Rn, const cx<T>* twM, const ColStoreNat<T>& out, hipStream_t st);
 
-// engine launchers (fft_row_*.hip / fft_col_*.hip); `var` = tuning variant (see fft_kernels.h)
-template <typename T> int launch_row_tiled(int logn, int var, const RowLoadNat<T>&, const RowStoreTiled<T>&, const cx<T>* tw, int nseq, int log_g, hipStream_t, int nbatch = 1);
-template <typename T> int launch_row_nat(int logn, int var, const RowLoadNat<T>&, const RowStoreNat<T>&, const cx<T>* tw, int nseq, int log_g, hipStream_t, int nbatch = 1);
+// engine launchers (fft_row_*.hip / fft_col_*.hip); `var` = column tiling (fft_kernels.h ColCfgSel; the row tiling is built_row_var there)
+template <typename T> int launch_row_tiled(int logn, const RowLoadNat<T>&, const RowStoreTiled<T>&, const cx<T>* tw, int nseq, int log_g, hipStream_t, int nbatch = 1);
+template <typename T> int launch_row_nat(int logn, const RowLoadNat<T>&, const RowStoreNat<T>&, const cx<T>* tw, int nseq, int log_g, hipStream_t, int nbatch = 1);
 template <typename T> int launch_col_tiled(int logm, int var, const ColLoadTiled<T>&, const ColStoreNat<T>&, const cx<T>* tw, int ntiles, int log_g, hipStream_t, int nbatch = 1);
 template <typename T> int launch_col_nat(int logm, int var, const ColLoadNat<T>&, const ColStoreNat<T>&, const cx<T>* tw, int ntiles, int log_g, hipStream_t, int nbatch = 1);
 template <typename T> int launch_col_mul(int logm, const ColLoadTiled<T>&, const MidMul<T>&, const ColStoreTiled<T>&, const cx<T>* tw, int ntiles, int log_g, hipStream_t, int nbatch = 1, int mode = 0);
 int pm_num_cus();   // compute units of the current device (cached per device)
 template <typename T> int launch_col_mul_crop(int logm, const ColLoadTiled<T>&, const MidMul<T>&, const ColStoreTiledCrop<T>&, const cx<T>* tw, int ntiles, int log_g, hipStream_t);
-template <typename T> int launch_row_from_tiled(int logn, int var, const RowLoadTiled<T>&, const RowStoreNat<T>&, const cx<T>* tw, int nseq, hipStream_t, int nbatch = 1);
+template <typename T> int launch_row_from_tiled(int logn, const RowLoadTiled<T>&, const RowStoreNat<T>&, const cx<T>* tw, int nseq, hipStream_t, int nbatch = 1);
 template <typename T> int launch_row_fold(int logn, const RowLoadNat<T>&, const RowStoreFold<T>&, const cx<T>* tw, int npairs, int log_g, hipStream_t, int nbatch = 1);
 template <typename T> int launch_row_unfold(int logn, const RowLoadFold<T>&, const RowStoreNat<T>&, const cx<T>* tw, int npairs, hipStream_t, int nbatch = 1);
 // tile width of the column pass; MUST match ColCfgSel in fft_kernels.h (CI * E)
@@ -123,29 +115,25 @@ inline int col_tile_width_for(int dtype, int logm, int var) {
     return ci * (dtype == PM_C64 ? 2 : 1);
 }
 
-// runtime tuning knobs (capi.hip): PM_TUNE="row_var=0,nt_in=1,nt_out=1" or pm_set_tuning().  They choose among equivalent tilings
-// and routes that each ship for some size / precision; one-off experiments live in tools/ (exp_*.cpp, exp_*.py), not here.
+// runtime tuning knobs (capi.hip): PM_TUNE="nt_in=1,nt_out=1,fold=0" or pm_set_tuning().  They choose among equivalent tilings
+// and routes that each ship for some size / precision; one-off experiments live in tools/ (exp_*.cpp, exp_*.py), not here.  Knobs whose
+// variants left the library have no field: capi_core.hip kRetired lists them with the one value each still accepts.
 struct Tuning {
     int col_var = -1;   // column-pass tiling (ColCfgSel): 0 64 B tiles, 2 128 B tiles for 2048-point columns, -1 auto (2 for the planes of a
                         // folded 4096-row complex128 transform)
-    int row_var = -1;   // (ignored since round 5) row-pass tiling (RowCfgSel): 0 plain, 1 half-LDS (re / im exchanged separately), 4 two rows per
-                        // thread, 5 one row per workgroup: the measured best per length and precision is the one that is built (row_variant() below)
     // non-temporal input loads / output stores: 0 off, 1 on, -1 auto (by array size vs the 256 MiB
     // Infinity Cache: measured on MI355X, streaming hints pay once the arrays no longer fit beside the
     // intermediate -- input from ~128 MiB, output from ~256 MiB; they cost a few % below that)
     int nt_in = -1, nt_out = -1;
     int log_k = -1;     // layout tiles of the intermediate are 2^log_k column-pass tiles wide; -1 auto
-    int gemm_3m = 1;          // complex products as three real MFMA chains (3M) instead of four
     int gemm_dma = 1;         // complex64 shapes that are multiples of 64 x 64 x 16 take the LDS-DMA kernel (cgemm_dma_kernel)
     int gemm_dma_wgs = 512;   // ... 128 x 128 tiles when there are at least this many, else 64 x 64 (two or three workgroups per CU hide each
                               // other's barriers); K is split until the launch has this many workgroups.  Measured (profiles/r02/exp_gemm_shapes.log):
                               // config 4 pair 148.5 us at 512 with 64 x 64 tiles against 155.5 (128 x 128, 256) and 164.1 (64 x 64, 256)
     int gemm_wk = 1;          // ... K split over wave groups INSIDE the workgroup when that fills the chip without slabs (cgemm.hip gemm_dma_plan):
-                              // bit 0 64 x 64 tiles with two K-groups (8 waves); removed in round 5 (experiments/README.md; the value is refused): bit 1 64 x 32 with two, bit 2 32 x 32 with four;
+                              // bit 0 64 x 64 tiles with two K-groups (8 waves) (bits 1 and 2 -- 64 x 32 with two, 32 x 32 with four -- left in round 5, experiments/README.md: refused);
                               // 0: round 2's forms only.  Config 4 (profiles/r03/exp_gemm_forms.log): 160.5 us at 0, 153.0 at 1, 155.3 at 2, 155.9 at 4
     int gemm_tile = 0;        // force its tile edge (64 / 128); 0 = auto
-    int gemm_bm = 64;         // rows of the GEMM workgroup tile (64 or 128)
-    int gemm_bk = 0;          // 0 default K-tile depth, 32 doubles it
     int gemm_min_wgs = 1024;   // split K until the GEMM launch has at least this many workgroups
     int row_log_g = 1;  // sibling group of row-pass workgroups (rows q .. q+2^g-1 on one XCD)
     int r2c = 1;             // real inputs take the Hermitian path where it is legal AND pays (capi.hip r2c_legal): real epilogues / centre
@@ -177,48 +165,22 @@ struct Tuning {
     int herm_t_fold = -1;     // ... its column pass folded (planes of M/2-point tiles): -1 auto (from 4096 rows), 0 never, 1 from 2048 rows
     int spectral = 8;         // pm_fft2_spectral: wavelengths per launch pair (fft_spectral.h; <= 8); 1: the plain loop of pm_fft2 calls
     int spectral_area_log = 24;   // ... for transforms of fewer than 2^this bins (capi.hip spectral_fast has the measurements)
-    int spectral2 = 0;        // removed in round 5 (experiments/README.md; the value is refused): groups of this many (2 .. 4) on the kernels that keep four waves per SIMD (fft_spectral2.h) where
-                              // the shape qualifies (complex64, rows of 1024 .. 4096 samples, every output bin kept); 0: round 3's forms.
-                              // Measured (profiles/r04/exp_spectral2.log, us per wavelength: loop / groups of 8 / these in groups of 2, 4):
-                              // 4096^2 108.3 / 106.1 / 111.8, 109.0; 2048^2 39.6 / 21.5 / 28.0, 23.7; 1024^2 24.1 / 10.4 / 16.9, 13.7
-    int spectral2_keep = 0;   // ... groups of 3 / 4: the raw (amplitude, OPD) values stay in registers between the pairs (three waves per SIMD)
-                              // instead of being read again from L2 / Infinity Cache
-    int spectral2_min_log = 0;    // ... for transforms of at least 2^this bins
-    int spectral_mode = 3;    // ... bit 0: its row pass keeps the packed map in registers, bit 1: its column pass accumulates in registers
     int colmul_mode = 3;      // middle pass of the fused chain at 2048-point column tiles (fft_kernels.h launch_col_mul_one): 3 lean addressing,
                               // two 512-thread workgroups per CU (126 VGPRs) where the pass qualifies (whole unrotated tiles, separable
                               // multiplier), else 0 = one tile per workgroup (184 VGPRs, one per CU); removed in round 5 (experiments/README.md; the value is refused): 1 the generic kernel under
                               // a 128-VGPR cap (spills), 2 persistent prefetching workgroups (twiddles / hy in LDS).  Measured
                               // (profiles/r03/exp_colmul.log, us, modes 0 / 1 / 2 / 3): middle pass of config 3 159.1 / 198.1 / 135.7 / 115.4;
                               // chain 4096^2 complex128 383 / 430 / 365 / 355, complex64 186 / 176 / 175 / 165, 2048^2 complex128 90 / 94 / 86 / 81
-    int engine_p8 = 0;        // removed in round 5 (experiments/README.md; the value is refused): the radix-8 engine (8 points per thread) for the folded 4096^2 complex64 transform: bit 0 its row pass,
-                              // bit 1 its column pass, bit 2 a 64-register cap (eight waves per SIMD) instead of 128
     int fft_stagger = -1, fft_stagger_col = -1, fft_stagger_mid = 0, fft_stagger_r2c = 0, fft_stagger_herm = -1;    // start-up stagger of the engine's plain row / column kernels (fft_kernels.h engine_log_g), units of 512 cycles x 0 .. 7; 0 = off, -1 = auto
-    int mix_fold = 0;         // removed in round 5 (experiments/README.md; the value is refused): a radix-2 step of a composite column transform folded into the mixed-radix row pass where the whole column's tile would
-                              // take a CU's LDS (capi.hip plan_fft2 mix_fold)
-    int mix_pers = 0;         // removed in round 5 (experiments/README.md; the value is refused): its column pass as persistent workgroups with the next tile prefetched where a CU holds one tile (mix_cols_pers_kernel)
     int mix_engine = 1;       // composite lengths with a compile-time plan on the register engine (fft_ce.h); 0: the general kernel everywhere
     int ce_rows_seqs = 0, ce_cols_seqs = 0, ce_log_g = -1;     // ... a built alternative of its rows / columns per workgroup (0: the default shape)
     int mix_stagger = 4;      // ... start-up stagger of the column kernel's workgroups in units of 512 cycles x 0 .. 7 where a CU holds one tile (fft_mixed.h MixShape::stagger); 0 = off
-    int mix_ablate = 0;       // removed in round 5 (experiments/README.md; the value is refused): timing-only ablations of the mixed-radix kernels (fft_mixed.h MixShape::ablate; results are wrong)
-    int two_units = 0;        // removed in round 5 (experiments/README.md; the value is refused): two units per workgroup in the passes of a 2048-point complex64 transform (bit 0 rows, bit 1 columns)
     int col_log_g = -1;       // sibling group of column-pass workgroups: 2^this adjacent tiles on one XCD back to back (-1: from the layout, capi.hip sibling_log_g)
     int stagger_group = 0;    // column kernels: the start-up stagger hashed per sibling group instead of per workgroup (fft_kernels.h engine_log_g)
     int batch_ws_mib = 128;   // batched transforms: fields per launch pair are chosen so their intermediates take
                              // at most this many MiB (measured best at 128; they should survive in the Infinity Cache between the passes)
 };
 Tuning& tuning();
-// measured on MI355X (profiles/r01/sweep*.log): the half-LDS variant wins for complex128 rows of 2048 points (24.6 vs 30.5 us)
-inline int row_variant(int dtype, int logn) {
-    // (the knob row_var is accepted and ignored since round 5: one tiling per length and precision is built, fft_kernels.h built_row_var)
-    // two rows per thread (variant 4) for complex64 from 4096 points: 53.5 -> 51.4 us at 4096^2, 226 -> 207 us at 8192^2;
-    // it loses for complex128 (register pressure) and makes no difference at 2048
-    if (dtype == PM_C64 && logn >= 12) return 4;
-    // 2048 points: complex64 one row per 128-thread workgroup (twice the workgroups: 17.9 -> 16.5 us at 2048^2), complex128 the
-    // half-LDS exchange (24.3 vs 28.3 us)
-    if (logn == 11) return dtype == PM_C64 ? 5 : 1;
-    return 0;
-}
 
 constexpr int kEngineMaxLog = 13;
 inline int engine_log2(int64_t n) {  // log2(n) if n is a power of two the engine handles, else -1

@@ -190,7 +190,7 @@ def test_product_never_imports_the_oracle():
 
 # ----------------------------------------------------------------------------- routes (pm_plan_explain: host logic, no GPU)
 
-def _route(lib, m, n, dt='c64', op=0, Q=None, real=False, mul=False, epi=0, batch=0, synth=False):
+def _desc(m, n, dt='c64', Q=None, real=False, mul=False, epi=0, batch=0, synth=False):
     from prysm_amd import _lib as L
     d = L.pm_fft2_desc()
     d.dtype, d.direction = (L.PM_C64 if dt == 'c64' else L.PM_C128), -1
@@ -210,6 +210,12 @@ def _route(lib, m, n, dt='c64', op=0, Q=None, real=False, mul=False, epi=0, batc
         d.mul_kind, d.mul, d.mul_x = L.PM_MUL_SEPARABLE, 16, 16
     if batch:
         d.batch, d.in_bstride, d.out_bstride = batch, m * n, m * n
+    return d
+
+
+def _route(lib, m, n, dt='c64', op=0, **kw):
+    from prysm_amd import _lib as L
+    d = _desc(m, n, dt, **kw)
     buf = ctypes.create_string_buffer(256)
     L.check(lib.pm_plan_explain(ctypes.byref(d), op, buf, 256))
     return buf.value.decode()
@@ -393,3 +399,52 @@ def test_explain_shows_the_launch_choices_the_plan_makes(lib):
         assert _route(lib, 4096, 4096).endswith(' g=2') and _route(lib, 8192, 8192, **mtf).endswith(' g=2')
     with L.tuning_local(col_log_g=7):     # the sibling group of the tiled column pass stops at 2^5
         assert _route(lib, 4096, 4096).endswith(' g=5')
+
+
+# PM_TUNE of the second child of the test below: one live knob
+_TUNE_LIVE = 'fold=0'
+# ... and of the first: the same behind a value of every retired knob that selected a removed variant
+_TUNE_RETIRED = 'mix_fold=1,mix_pers=1,mix_ablate=15,two_units=3,engine_p8=7,spectral2=4,gemm_3m=0,spectral_mode=0,' + _TUNE_LIVE
+_CHILD = """
+import ctypes, sys
+sys.path[:0] = [%r, %r]
+import test_capi_symbols as t
+from prysm_amd import _lib as L
+lib = L.load()
+for m in (3000, 4096):      # a composite grid with every row stored (what the removed fold of the mixed-radix passes matched); the engine's
+    print(t._route(lib, m, m))
+    print('ws', lib.pm_fft2_workspace(ctypes.byref(t._desc(m, m))))
+""" % (ROOT, os.path.dirname(os.path.abspath(__file__)))
+
+
+def _plans_under(tune):
+    import subprocess
+    import sys
+    res = subprocess.run([sys.executable, '-c', _CHILD], env=dict(os.environ, PM_TUNE=tune), capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    return res.stdout.splitlines()
+
+
+def test_retired_knobs_are_refused_on_every_way_in(lib):
+    """The knobs of the variants that left the library in round 5 (experiments/README.md) have ONE table (capi_core.hip kRetired) behind
+    pm_set_tuning, pm_set_tuning_local and the PM_TUNE environment variable.  PM_TUNE used to skip the refusal: mix_fold=1 made the planner
+    fold a composite grid whose row kernel no longer folds.  Two fresh processes, one with a retired value of every such knob in front
+    of fold=0 and one with fold=0 alone, must plan the same routes and workspaces -- and fold=0 must still have taken effect."""
+    from prysm_amd import _lib as L
+    got, want = _plans_under(_TUNE_RETIRED), _plans_under(_TUNE_LIVE)
+    assert len(want) == 4 and got == want, (got, want)
+    assert 'rows=mixed-radix-registers(3000)' in want[0] and 'cols=mixed-radix-registers(3000)' in want[0] and want[1] == 'ws 72192000'
+    assert 'route=engine ' in want[2] and 'cols=stockham(4096)' in want[2] and want[3] == 'ws 134217728'
+    refused = ((b'mix_fold', 1), (b'mix_pers', 1), (b'two_units', 1), (b'engine_p8', 1), (b'spectral2', 2), (b'colmul_mode', 1), (b'colmul_mode', 2),
+               (b'gemm_wk', 2), (b'gemm_3m', 0), (b'mix_ablate', 1), (b'spectral_mode', 0), (b'gemm_bm', 128), (b'gemm_bk', 32))
+    accepted = ((b'mix_fold', 0), (b'mix_pers', 0), (b'two_units', 0), (b'engine_p8', 0), (b'spectral2', 0), (b'mix_ablate', 0), (b'gemm_3m', 1),
+                (b'gemm_bm', 64), (b'gemm_bk', 0), (b'spectral_mode', 3), (b'row_var', 0), (b'row_var', 4), (b'row_var', -1),
+                (b'colmul_mode', 3), (b'colmul_mode', 0), (b'gemm_wk', 1), (b'stagger_group', 1), (b'no_such_knob', 5))
+    try:
+        for key, v in refused:
+            assert lib.pm_set_tuning_local(key, v) == L.PM_ERR_UNSUPPORTED, key
+            assert key in lib.pm_last_error() and b'experiments/README.md' in lib.pm_last_error()
+        for key, v in accepted:
+            assert lib.pm_set_tuning_local(key, v) == 0, key
+    finally:
+        lib.pm_reset_tuning_local()

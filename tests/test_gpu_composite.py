@@ -416,6 +416,26 @@ def test_composite_engine_plans_vs_numpy_and_general_kernel(pa, n, cdt):
         assert rel_max(got[1], got[0]) < tol
 
 
+@pytest.mark.parametrize('cdt', [np.complex64, np.complex128])
+def test_general_kernels_on_the_smallest_grid_whose_column_tile_fills_a_cu(pa, cdt):
+    """1500 x 48 with every row stored: the tile of the general column kernel (eight complex64 / four complex128 columns of 1500 points,
+    96 KB) is above 80 KiB of LDS -- one 1024-thread workgroup per CU, the smallest grid that the removed fold and persistent forms of the
+    mixed-radix passes (experiments/README.md) would have matched.  Forward, and inverse with a rotated output, against numpy in fp64, on
+    the general row and column kernels (knob mix_engine = 0) and on the default route."""
+    from prysm_amd import _lib, _ops
+    shape = (1500, 48)
+    rng = np.random.default_rng(1548)
+    tol = TOL32 if cdt == np.complex64 else TOL64
+    x = (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(cdt)
+    xd = torch.from_numpy(x).cuda()
+    for direction, out_shift in ((-1, (0, 0)), (+1, (750, 24))):
+        want = _ce_ref(x, shape, (0, 0), (0, 0), out_shift, direction)
+        for eng in (0, 1):
+            with _lib.tuning_local(mix_engine=eng):
+                got = _ops.fft2(xd, direction=direction, scale=1.0, out_shift=out_shift).cpu().numpy()
+            assert got.dtype == cdt and rel_max(got, want) < tol, (cdt.__name__, direction, eng)
+
+
 @pytest.mark.parametrize('n,cdt', [(1000, np.complex64), (1500, np.complex128), (3000, np.complex64)])
 def test_composite_engine_intensity_epilogues(pa, n, cdt):
     """|.|^2 and weight |.|^2 accumulated (Wavefront.intensity, the polychromatic sum) in the engine's column store."""

@@ -435,10 +435,9 @@ static void bench_fft2(int64_t n, int64_t in_n, int epi) {
 // sweep of the tuning knobs on one transform size: configurations are timed round-robin for several
 // rounds in ONE process (interleaved A/B, cdna guide rule 24); min and median of the whole-transform time
 struct Knobs {
-    int row_var, col_var, nt_in, nt_out, log_k, row_log_g;
+    int col_var, nt_in, nt_out, log_k, row_log_g;
 };
 static void apply(const Knobs& k) {
-    pm_set_tuning("row_var", k.row_var);
     pm_set_tuning("col_var", k.col_var);
     pm_set_tuning("nt_in", k.nt_in);
     pm_set_tuning("nt_out", k.nt_out);
@@ -495,12 +494,12 @@ static void sweep_fft2(int64_t n, const std::vector<Knobs>& cfgs, int rounds) {
         std::sort(t[c].begin(), t[c].end());
         const double mn = t[c].front(), med = t[c][t[c].size() / 2];
         const Knobs& k = cfgs[c];
-        printf("SWEEP %s N=%lld row_var=%d col_var=%d nt_in=%d nt_out=%d log_k=%d row_log_g=%d : total min %.1f med %.1f us "
+        printf("SWEEP %s N=%lld col_var=%d nt_in=%d nt_out=%d log_k=%d row_log_g=%d : total min %.1f med %.1f us "
                "(%.1f%% of 8TB/s at min) ; passes %.1f + %.1f us\n",
-               sizeof(T) == 4 ? "c64" : "c128", (long long)n, k.row_var, k.col_var, k.nt_in, k.nt_out, k.log_k, k.row_log_g, mn, med,
+               sizeof(T) == 4 ? "c64" : "c128", (long long)n, k.col_var, k.nt_in, k.nt_out, k.log_k, k.row_log_g, mn, med,
                alg / mn / 1e6 / 8000 * 100, p1[c], p2[c]);
     }
-    apply(Knobs{-1, 0, -1, -1, -1, 1});
+    apply(Knobs{0, -1, -1, -1, 1});
     HIPCHECK(hipFree(din));
     HIPCHECK(hipFree(dout));
     HIPCHECK(hipFree(ws));
@@ -509,7 +508,7 @@ static void sweep_fft2(int64_t n, const std::vector<Knobs>& cfgs, int rounds) {
 // generic interleaved A/B: "tune N c64|c128 rounds cfg cfg ..." with cfg = "key=val,key=val" (pm_set_tuning keys; keys not
 // named in a cfg are reset to their defaults first)
 static void set_cfg(const std::string& cfg) {
-    static const char* defaults = "row_var=-1,col_var=-1,nt_in=-1,nt_out=-1,log_k=-1,row_log_g=1,fold=-1";
+    static const char* defaults = "col_var=-1,nt_in=-1,nt_out=-1,log_k=-1,row_log_g=1,fold=-1";
     for (const std::string& src : {std::string(defaults), cfg}) {
         size_t i = 0;
         while (i < src.size()) {
@@ -784,7 +783,7 @@ int main(int argc, char** argv) {
     printf("device: %s (%s) CUs=%d LDS/block=%zu version=%d\n", prop.name, prop.gcnArchName, prop.multiProcessorCount,
            prop.sharedMemPerBlock, pm_version());
     if (mode == "big") {
-        const std::vector<Knobs> cfg = {{-1, 0, -1, -1, -1, 1}, {-1, 0, -1, 0, -1, 1}, {-1, 0, 0, 0, -1, 1}, {-1, 0, -1, 0, 3, 1}, {-1, 0, -1, 0, 1, 1}};
+        const std::vector<Knobs> cfg = {{0, -1, -1, -1, 1}, {0, -1, 0, -1, 1}, {0, 0, 0, -1, 1}, {0, -1, 0, 3, 1}, {0, -1, 0, 1, 1}};
         sweep_fft2<float>(8192, cfg, 2);
         return 0;
     }
@@ -901,17 +900,11 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (mode == "sweep") {
-        const std::vector<Knobs> c64 = {
-            {0, 0, -1, -1, -1, 1}, {1, 0, -1, -1, -1, 1}, {2, 0, -1, -1, -1, 1},
-        };
-        sweep_fft2<float>(4096, c64, 3);
-        const std::vector<Knobs> c128 = {
-            {-1, 0, -1, -1, -1, 1},
-        };
-        sweep_fft2<double>(4096, c128, 2);
-        const std::vector<Knobs> small = {{0, 0, -1, -1, -1, 1}, {1, 0, -1, -1, -1, 1}};
-        sweep_fft2<float>(2048, small, 3);
-        sweep_fft2<double>(2048, small, 3);
+        const std::vector<Knobs> dflt = {{0, -1, -1, -1, 1}};
+        sweep_fft2<float>(4096, dflt, 3);
+        sweep_fft2<double>(4096, dflt, 2);
+        sweep_fft2<float>(2048, dflt, 3);
+        sweep_fft2<double>(2048, dflt, 3);
         return 0;
     }
     if (mode != "bench") {
