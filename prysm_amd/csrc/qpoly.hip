@@ -11,10 +11,10 @@
 // Im z^|m| need no trigonometry in the loop.  Radial tables (Qbfs, Qcon) take PM_QPOLY_RADIAL points: u only, no angle read.  The
 // step index is uniform, so the table is read through the scalar cache.  A step whose slot is outside [0, nmodes) writes nothing.
 //
-// The tile, its 16-byte loads and stores, the wave reduction, the fixed-order second stage and the host's launch helpers are
-// zernike_walk.h's; the projection is pm_zernike_project's scheme: per-workgroup partials in the caller's workspace, then a
-// fixed-order sum.  No atomics, so every run and every graph replay gives the same bits.
-#include "zernike_walk.h"
+// The tile, its 16-byte loads and stores, the projection's reduction around qwalk, its fixed-order second stage and the host's launch
+// helpers are modal_tile.h's: per-workgroup partials in the caller's workspace, then a fixed-order sum.  No atomics, so every run and
+// every graph replay gives the same bits.
+#include "modal_tile.h"
 
 namespace pm {
 namespace {
@@ -180,64 +180,28 @@ __global__ __launch_bounds__(kThreads) void qpoly_sum_kernel(int64_t npts, int c
 }
 
 // ---------------------------------------------------------------- projection: one partial per (workgroup, b, k)
-// As zernike_project_kernel: each wave sums its 64 x kVec points per step, reduces over its lanes and adds the total into an LDS slot
-// of its own, (wave, b, k); the workgroup adds its waves in order at the end and stores partial[group][b0 + b][k] (row length
-// ld = B * nmodes).  The butterflies of E = 8 / NB consecutive steps run together.
+// The reduction of modal_tile.h around qwalk(): partial[group][b0 + b][k], row length ld = B * nmodes.
 template <typename T, int NB>
 __global__ __launch_bounds__(kThreads) void qpoly_project_kernel(int64_t npts, int coords, const T* __restrict__ u, const T* __restrict__ v,
                                                                  const QStep<T>* __restrict__ table, int nsteps, int nmodes,
                                                                  const T* __restrict__ g, T* __restrict__ partial, int64_t ld, int vec) {
-    constexpr int E = 8 / NB;
     extern __shared__ __align__(16) unsigned char smem[];
-    T* sacc = reinterpret_cast<T*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nacc = NB * nmodes;
-    for (int e = tid; e < kWaves * nacc; e += kThreads) sacc[e] = T(0);
-    __syncthreads();
+    T* sacc = project_begin<T>(smem, nacc, tid);
     T* wacc = sacc + wave * nacc;
-    // the wave stays together through the loop (a shuffle needs every lane) and masks its own tail
     for (int64_t base = wave_tile(wave); base < npts; base += int64_t(gridDim.x) * kThreads * kVec) {
         const bool full = vec && base + 64 * kVec <= npts;
-        T uu[kVec], vv[kVec], gg[NB][kVec], red[NB][E];
-        int slot[E];
+        T uu[kVec], vv[kVec], gg[NB][kVec];
+        ProjectStep<T, NB> step;
         load_coords(coords, u, v, base, lane, npts, full, uu, vv);
 #pragma unroll
         for (int b = 0; b < NB; ++b) load_pts(g + int64_t(b) * npts, base, lane, npts, full, gg[b]);
-#pragma unroll
-        for (int j = 0; j < E; ++j) slot[j] = -1;
-        qwalk<E>(coords, uu, vv, table, nsteps, nmodes,
-                 [&](int j, int k, const T z[kVec]) {
-                     slot[j] = k;
-#pragma unroll
-                     for (int b = 0; b < NB; ++b) {
-                         T s = T(0);
-#pragma unroll
-                         for (int q = 0; q < kVec; ++q) s += gg[b][q] * z[q];
-                         red[b][j] = s;
-                     }
-                 },
-                 [&] {
-#pragma unroll
-                     for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-                         for (int j = 0; j < E; ++j)
-#pragma unroll
-                             for (int b = 0; b < NB; ++b) red[b][j] += __shfl_xor(red[b][j], off);
-#pragma unroll
-                     for (int j = 0; j < E; ++j) {
-                         if (slot[j] >= 0 && lane == 0)
-#pragma unroll
-                             for (int b = 0; b < NB; ++b) wacc[b * nmodes + slot[j]] += red[b][j];
-                         slot[j] = -1;
-                     }
-                 });
+        step.clear();
+        qwalk<ProjectStep<T, NB>::E>(coords, uu, vv, table, nsteps, nmodes, [&](int j, int k, const T z[kVec]) { step.emit(j, k, gg, z); },
+                                     [&] { step.flush(wacc, nmodes, lane); });
     }
-    __syncthreads();
-    for (int o = tid; o < nacc; o += kThreads) {
-        T s = sacc[o];
-        for (int w = 1; w < kWaves; ++w) s += sacc[w * nacc + o];
-        partial[int64_t(blockIdx.x) * ld + o] = s;
-    }
+    project_end(sacc, nacc, tid, [&](int o, T s) { partial[int64_t(blockIdx.x) * ld + o] = s; });
 }
 
 int check_walk(const char* who, int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
@@ -296,38 +260,23 @@ int pm_qpoly_sum(int32_t dtype, int32_t coords, int64_t npts, const void* u, con
 
 size_t pm_qpoly_project_workspace(int32_t dtype, int64_t npts, int64_t nmodes, int64_t batch) {
     if (!real_dtype(dtype) || npts < 0 || nmodes < 0 || batch < 0) return 0;
-    return size_t(project_groups(npts)) * size_t(batch) * size_t(nmodes) * elem_of(dtype);
+    return project_workspace_bytes(dtype, npts, size_t(batch) * size_t(nmodes));
 }
 
 int pm_qpoly_project(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
                      int64_t nmodes, int64_t batch, const void* databar, void* out, void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_walk("pm_qpoly_project", dtype, coords, npts, u, v, table, nsteps, nmodes)) return rc;
     if (!out || !databar || batch < 0) return fail(PM_ERR_ARG, "pm_qpoly_project: bad argument (null pointer or negative batch)");
-    if (batch * nmodes > INT32_MAX) return fail(PM_ERR_ARG, "pm_qpoly_project: batch * nmodes is too large");
-    if (project_lds(1, nmodes, elem_of(dtype)) > kProjectLds)
-        return fail(PM_ERR_UNSUPPORTED, "pm_qpoly_project: %lld modes do not fit the workgroup's accumulators", (long long)nmodes);
-    if (batch == 0 || nmodes == 0) return 0;
-    const size_t need = pm_qpoly_project_workspace(dtype, npts, nmodes, batch);
-    if (!workspace || workspace_bytes < need)
-        return fail(PM_ERR_WORKSPACE, "pm_qpoly_project: workspace of %zu bytes is smaller than the %zu pm_qpoly_project_workspace asks for",
-                    workspace_bytes, need);
-    return by_rdtype(dtype, "pm_qpoly_project", [&](auto real) {
-        using T = decltype(real);
-        const T *up = static_cast<const T*>(u), *vp = static_cast<const T*>(v), *g = static_cast<const T*>(databar);
-        const QStep<T>* steps = static_cast<const QStep<T>*>(table);
-        T* partial = static_cast<T*>(workspace);
-        hipStream_t st = PM_STREAM(stream);
-        const int64_t groups = project_groups(npts), nout = batch * nmodes;
-        const dim3 grid{unsigned(groups)}, block{kThreads};
-        const int vec = vec_ok(npts, {u, v, databar});
-        for (int64_t b0 = 0; b0 < batch;)
-            b0 += by_nb(batch - b0, project_nb(dtype, nmodes, batch), [&](auto nb) {
-                hipLaunchKernelGGL((qpoly_project_kernel<T, decltype(nb)::value>), grid, block, project_lds(nb, nmodes, sizeof(T)), st, npts,
-                                   coords, up, vp, steps, int(nsteps), int(nmodes), g + b0 * npts, partial + b0 * nmodes, nout, vec);
-            });
-        hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(nout)), block, 0, st, groups, nout, partial, static_cast<T*>(out));
-        return int(hipGetLastError());
-    });
+    const int vec = vec_ok(npts, {u, v, databar});
+    return launch_project("pm_qpoly_project", "nmodes", "modes", dtype, npts, nmodes, batch, nmodes, 0, out, workspace, workspace_bytes, stream,
+                          kMaxProjectGroups, [&](auto real, auto nb, int64_t b0, int64_t groups, size_t lds, hipStream_t st) {
+                              using T = decltype(real);
+                              hipLaunchKernelGGL((qpoly_project_kernel<T, decltype(nb)::value>), dim3(unsigned(groups)), dim3(kThreads), lds, st,
+                                                 npts, coords, static_cast<const T*>(u), static_cast<const T*>(v),
+                                                 static_cast<const QStep<T>*>(table), int(nsteps), int(nmodes),
+                                                 static_cast<const T*>(databar) + b0 * npts, static_cast<T*>(workspace) + b0 * nmodes,
+                                                 batch * nmodes, vec);
+                          });
 }
 
 }  // extern "C"

@@ -14,7 +14,8 @@
 // (slot, -1: walked, not written).  The step index is uniform, so the table is read through the scalar cache.
 //
 // The reductions are deterministic as in zernike.hip: partials in a fixed order into the caller's workspace, then a fixed-order sum.
-#include "zernike_walk.h"
+// The tile, the 1-D projection's reduction around rwalk, its second stage and its launcher are modal_tile.h's.
+#include "modal_tile.h"
 
 namespace pm {
 namespace {
@@ -156,26 +157,22 @@ __global__ __launch_bounds__(kThreads) void recur_sum_kernel(int64_t npts, int r
 }
 
 // ---------------------------------------------------------------- projection: one partial per (workgroup, b, k)
-// As zernike_project_kernel: a wave sums its 64 x kVec points per step, reduces over its lanes and adds the total into an LDS slot of
-// its own; the workgroup adds its waves in order and stores partial[group][b0 + b][k].  With der the derivative track is projected,
-// g first multiplied by the chain factor of the R2 form (g 4 x / R^2 + g2 4 y / R^2).
+// The reduction of modal_tile.h around rwalk(): partial[group][b0 + b][k], row length ld = B * nout.  With der the derivative track
+// is projected, g first multiplied by the chain factor of the R2 form (g 4 x / R^2 + g2 4 y / R^2).
 template <typename T, int NB>
 __global__ __launch_bounds__(kThreads) void recur_project_kernel(int64_t npts, int r2, T inv_r2, const T* __restrict__ u, const T* __restrict__ v,
                                                                  const RStep<T>* __restrict__ table, int nsteps, int nout, int der,
                                                                  const T* __restrict__ g, const T* __restrict__ g2, T* __restrict__ partial,
                                                                  int64_t ld, int vec) {
-    constexpr int E = 8 / NB;
     extern __shared__ __align__(16) unsigned char smem[];
-    T* sacc = reinterpret_cast<T*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nacc = NB * nout;
-    for (int e = tid; e < kWaves * nacc; e += kThreads) sacc[e] = T(0);
-    __syncthreads();
+    T* sacc = project_begin<T>(smem, nacc, tid);
     T* wacc = sacc + wave * nacc;
     for (int64_t base = wave_tile(wave); base < npts; base += int64_t(gridDim.x) * kThreads * kVec) {
         const bool full = vec && base + 64 * kVec <= npts;
-        T uu[kVec], vv[kVec] = {}, X[kVec], gg[NB][kVec], red[NB][E];
-        int slot[E];
+        T uu[kVec], vv[kVec] = {}, X[kVec], gg[NB][kVec];
+        ProjectStep<T, NB> step;
         load_pts(u, base, lane, npts, full, uu);
         if (r2) load_pts(v, base, lane, npts, full, vv);
         recur_arg(r2, inv_r2, uu, vv, X);
@@ -189,60 +186,13 @@ __global__ __launch_bounds__(kThreads) void recur_project_kernel(int64_t npts, i
                 for (int q = 0; q < kVec; ++q) gg[b][q] = (gg[b][q] * uu[q] + hh[q] * vv[q]) * (T(4) * inv_r2);
             }
         }
-#pragma unroll
-        for (int j = 0; j < E; ++j) slot[j] = -1;
-        rwalk<E, true>(X, table, nsteps, nout,
-                       [&](int j, int k, const T p[kVec], const T d[kVec]) {
-                           slot[j] = k;
-#pragma unroll
-                           for (int b = 0; b < NB; ++b) {
-                               T s = T(0);
-#pragma unroll
-                               for (int q = 0; q < kVec; ++q) s += gg[b][q] * (der ? d[q] : p[q]);
-                               red[b][j] = s;
-                           }
-                       },
-                       [&] {
-#pragma unroll
-                           for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-                               for (int j = 0; j < E; ++j)
-#pragma unroll
-                                   for (int b = 0; b < NB; ++b) red[b][j] += __shfl_xor(red[b][j], off);
-#pragma unroll
-                           for (int j = 0; j < E; ++j) {
-                               if (slot[j] >= 0 && lane == 0)
-#pragma unroll
-                                   for (int b = 0; b < NB; ++b) wacc[b * nout + slot[j]] += red[b][j];
-                               slot[j] = -1;
-                           }
-                       });
+        step.clear();
+        rwalk<ProjectStep<T, NB>::E, true>(
+            X, table, nsteps, nout,
+            [&](int j, int k, const T p[kVec], const T d[kVec]) { step.emit_each(j, k, gg, [&](int q) { return der ? d[q] : p[q]; }); },
+            [&] { step.flush(wacc, nout, lane); });
     }
-    __syncthreads();
-    for (int o = tid; o < nacc; o += kThreads) {
-        T s = sacc[o];
-        for (int w = 1; w < kWaves; ++w) s += sacc[w * nacc + o];
-        partial[int64_t(blockIdx.x) * ld + o] = s;
-    }
-}
-
-// second stage of the projection: out[o] (+)= sum over groups of partial[group][o], in the order of reduce_partials_kernel
-template <typename T>
-__global__ __launch_bounds__(kThreads) void recur_reduce_kernel(int64_t ngroups, int64_t nout, const T* __restrict__ partial, int accumulate,
-                                                                T* __restrict__ out) {
-    __shared__ T sw[kWaves];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t o = blockIdx.x;
-    T s = T(0);
-    for (int64_t gi = tid; gi < ngroups; gi += kThreads) s += partial[gi * nout + o];
-    s = wave_sum(s);
-    if (lane == 0) sw[wave] = s;
-    __syncthreads();
-    if (tid == 0) {
-        T t = sw[0];
-        for (int w = 1; w < kWaves; ++w) t += sw[w];
-        out[o] = accumulate ? out[o] + t : t;
-    }
+    project_end(sacc, nacc, tid, [&](int o, T s) { partial[int64_t(blockIdx.x) * ld + o] = s; });
 }
 
 // ---------------------------------------------------------------- separable sum on a rows x cols grid
@@ -594,7 +544,7 @@ int pm_recur_sum(int32_t dtype, int32_t form, int64_t npts, const void* u, const
 
 size_t pm_recur_project_workspace(int32_t dtype, int64_t npts, int64_t nout, int64_t batch) {
     if (!real_dtype(dtype) || npts < 0 || nout < 0 || batch < 0) return 0;
-    return size_t(project_groups(npts)) * size_t(batch) * size_t(nout) * elem_of(dtype);
+    return project_workspace_bytes(dtype, npts, size_t(batch) * size_t(nout));
 }
 
 int pm_recur_project(int32_t dtype, int32_t form, int64_t npts, const void* u, const void* v, double radius, const void* table, int64_t nsteps,
@@ -604,36 +554,17 @@ int pm_recur_project(int32_t dtype, int32_t form, int64_t npts, const void* u, c
     if (!out || !databar || batch < 0) return fail(PM_ERR_ARG, "pm_recur_project: bad argument (null pointer or negative batch)");
     if (databar2 && !(der && form == PM_RECUR_R2))
         return fail(PM_ERR_ARG, "pm_recur_project: databar2 is the dy adjoint of form PM_RECUR_R2 with der set");
-    if (batch * nout > INT32_MAX) return fail(PM_ERR_ARG, "pm_recur_project: batch * nout is too large");
-    if (project_lds(1, nout, elem_of(dtype)) > kProjectLds)
-        return fail(PM_ERR_UNSUPPORTED, "pm_recur_project: %lld orders do not fit the workgroup's accumulators", (long long)nout);
-    if (batch == 0 || nout == 0) return 0;
-    const size_t need = pm_recur_project_workspace(dtype, npts, nout, batch);
-    if (!workspace || workspace_bytes < need)
-        return fail(PM_ERR_WORKSPACE, "pm_recur_project: workspace of %zu bytes is smaller than the %zu pm_recur_project_workspace asks for",
-                    workspace_bytes, need);
-    return by_rdtype(dtype, "pm_recur_project", [&](auto real) {
-        using T = decltype(real);
-        const int r2 = form == PM_RECUR_R2;
-        const T *up = static_cast<const T*>(u), *vp = static_cast<const T*>(v);
-        const T *g = static_cast<const T*>(databar), *g2 = static_cast<const T*>(databar2);
-        const RStep<T>* steps = static_cast<const RStep<T>*>(table);
-        T* partial = static_cast<T*>(workspace);
-        hipStream_t st = PM_STREAM(stream);
-        const int64_t groups = project_groups(npts), total = batch * nout;
-        const dim3 grid{unsigned(groups)}, block{kThreads};
-        const int vec = vec_ok(npts, {u, v, databar, databar2});
-        const T inv_r2 = T(r2 ? 1.0 / (radius * radius) : 1.0);
-        for (int64_t b0 = 0; b0 < batch;)
-            b0 += by_nb(batch - b0, project_nb(dtype, nout, batch), [&](auto nb) {
-                hipLaunchKernelGGL((recur_project_kernel<T, decltype(nb)::value>), grid, block, project_lds(nb, nout, sizeof(T)), st, npts, r2,
-                                   inv_r2, up, vp, steps, int(nsteps), int(nout), der != 0, g + b0 * npts, g2 ? g2 + b0 * npts : nullptr,
-                                   partial + b0 * nout, total, vec);
-            });
-        hipLaunchKernelGGL(recur_reduce_kernel<T>, dim3(unsigned(total)), block, 0, st, groups, total, partial, accumulate != 0,
-                           static_cast<T*>(out));
-        return int(hipGetLastError());
-    });
+    const int r2 = form == PM_RECUR_R2, vec = vec_ok(npts, {u, v, databar, databar2});
+    return launch_project("pm_recur_project", "nout", "orders", dtype, npts, nout, batch, nout, accumulate, out, workspace, workspace_bytes, stream,
+                          kMaxProjectGroups, [&](auto real, auto nb, int64_t b0, int64_t groups, size_t lds, hipStream_t st) {
+                              using T = decltype(real);
+                              const T *g = static_cast<const T*>(databar), *g2 = static_cast<const T*>(databar2);
+                              hipLaunchKernelGGL((recur_project_kernel<T, decltype(nb)::value>), dim3(unsigned(groups)), dim3(kThreads), lds, st,
+                                                 npts, r2, T(r2 ? 1.0 / (radius * radius) : 1.0), static_cast<const T*>(u),
+                                                 static_cast<const T*>(v), static_cast<const RStep<T>*>(table), int(nsteps), int(nout), der != 0,
+                                                 g + b0 * npts, g2 ? g2 + b0 * npts : nullptr, static_cast<T*>(workspace) + b0 * nout,
+                                                 batch * nout, vec);
+                          });
 }
 
 int pm_recur2_sum(int32_t dtype, int64_t rows, int64_t cols, const void* x, const void* y, const void* xtable, int64_t nx, const void* ytable,

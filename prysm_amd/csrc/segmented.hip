@@ -7,8 +7,8 @@
 //    wave-uniform, so the Zernike walk (zernike_walk.h) is shared by the whole wave.  A wave whose points have no segment left in a
 //    pass stops there (the lists are packed to the front).
 //  - pm_segment_project: out[b][s][k] = sum over the window of s of mask_s[p] Z_{s,k}[p] g[b][p].  Segment-major: workgroup (i, s)
-//    takes slice i of segment s's window, so the segment is uniform; the per-workgroup partials are summed by a second launch in a
-//    fixed order, as pm_zernike_project does.  No atomics: bitwise reproducible.
+//    takes slice i of segment s's window, so the segment is uniform; the reduction, the second launch that sums the per-workgroup
+//    partials in a fixed order and the launcher are modal_tile.h's, as for pm_zernike_project.  No atomics: bitwise reproducible.
 //
 // Z_{s,k} comes from one of two sources, a template parameter of both kernels: the Zernike table walk at the local coordinates of the
 // segment's grid source ((x - cx) / nr, (y - cy) / nr at the same position in the source's window), or a strided read of a stored
@@ -149,9 +149,8 @@ __global__ __launch_bounds__(kThreads) void segment_compose_kernel(int rows, int
 }
 
 // ---------------------------------------------------------------- projection: segment-major, one partial per (workgroup, b, s, k)
-// Workgroup (blockIdx.x, s) walks its slice of the window of s with the reduction of zernike_project_kernel: per step a lane sum, a
-// butterfly over the wave, the wave's LDS slot (wave, b, k); the waves are added in order at the end into
-// partial[blockIdx.x][b0 + b][s][k] (row length ld = B * nseg * nmodes).
+// Workgroup (blockIdx.x, s) walks its slice of the window of s with the reduction of modal_tile.h around seg_modes(); g is weighted
+// by the mask as it is loaded.  The partials go to partial[blockIdx.x][b0 + b][s][k] (row length ld = B * nseg * nmodes).
 template <int SRC, typename T, int NB>
 __global__ __launch_bounds__(kThreads) void segment_project_kernel(int rows, int cols, const T* __restrict__ x, const T* __restrict__ y,
                                                                    int nseg, const SegDesc* __restrict__ plan, const T* __restrict__ masks,
@@ -159,22 +158,19 @@ __global__ __launch_bounds__(kThreads) void segment_project_kernel(int rows, int
                                                                    const T* __restrict__ basis, const T* __restrict__ g,
                                                                    T* __restrict__ partial, int64_t ld) {
     using RT = Runs<T>;
-    constexpr int E = 8 / NB;
     extern __shared__ __align__(16) unsigned char smem[];
-    T* sacc = reinterpret_cast<T*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = blockIdx.y;
     const SegDesc d = plan[s];
     const int64_t npts = int64_t(rows) * cols, hwin = int64_t(d.h) * d.w;
     const int nacc = NB * nmodes;
-    for (int e = tid; e < kWaves * nacc; e += kThreads) sacc[e] = T(0);
-    __syncthreads();
+    T* sacc = project_begin<T>(smem, nacc, tid);
     T* wacc = sacc + wave * nacc;
     for (int64_t base = wave_tile(wave); base < hwin; base += int64_t(gridDim.x) * kThreads * kVec) {
-        T u[kVec], v[kVec], wg[NB][kVec], red[NB][E];
+        T u[kVec], v[kVec], wg[NB][kVec];
         const T* bp[kVec];
         int64_t hw[kVec];
-        int slot[E];
+        ProjectStep<T, NB> step;
 #pragma unroll
         for (int q = 0; q < kVec; ++q) {
             const int64_t i = RT::at(base, lane, q);
@@ -192,42 +188,14 @@ __global__ __launch_bounds__(kThreads) void segment_project_kernel(int rows, int
                 seg_point<SRC>(d, wr, wc, li, cols, x, y, basis, u[q], v[q], bp[q], hw[q]);
             }
         }
-#pragma unroll
-        for (int j = 0; j < E; ++j) slot[j] = -1;
-        seg_modes<SRC, E>(u, v, bp, hw, table, nsteps, nmodes,
-                          [&](int j, int k, const T z[kVec]) {
-                              slot[j] = k;
-#pragma unroll
-                              for (int b = 0; b < NB; ++b) {
-                                  T sum = T(0);
-#pragma unroll
-                                  for (int q = 0; q < kVec; ++q) sum += wg[b][q] * z[q];
-                                  red[b][j] = sum;
-                              }
-                          },
-                          [&] {
-#pragma unroll
-                              for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-                                  for (int j = 0; j < E; ++j)
-#pragma unroll
-                                      for (int b = 0; b < NB; ++b) red[b][j] += __shfl_xor(red[b][j], off);
-#pragma unroll
-                              for (int j = 0; j < E; ++j) {
-                                  if (slot[j] >= 0 && lane == 0)
-#pragma unroll
-                                      for (int b = 0; b < NB; ++b) wacc[b * nmodes + slot[j]] += red[b][j];
-                                  slot[j] = -1;
-                              }
-                          });
+        step.clear();
+        seg_modes<SRC, ProjectStep<T, NB>::E>(u, v, bp, hw, table, nsteps, nmodes, [&](int j, int k, const T z[kVec]) { step.emit(j, k, wg, z); },
+                                              [&] { step.flush(wacc, nmodes, lane); });
     }
-    __syncthreads();
-    for (int o = tid; o < nacc; o += kThreads) {
-        T sum = sacc[o];
-        for (int w = 1; w < kWaves; ++w) sum += sacc[w * nacc + o];
+    project_end(sacc, nacc, tid, [&](int o, T sum) {
         const int b = o / nmodes, k = o - b * nmodes;
         partial[int64_t(blockIdx.x) * ld + (int64_t(b) * nseg + s) * nmodes + k] = sum;
-    }
+    });
 }
 
 int check_common(const char* who, int32_t dtype, int32_t source, int64_t rows, int64_t cols, const void* x, const void* y, int64_t nseg,
@@ -317,7 +285,7 @@ int pm_segment_compose(int32_t dtype, int32_t source, int64_t rows, int64_t cols
 
 size_t pm_segment_project_workspace(int32_t dtype, int64_t window_pts, int64_t nseg, int64_t nmodes, int64_t batch) {
     if (!real_dtype(dtype) || window_pts < 0 || nseg < 0 || nmodes < 0 || batch < 0) return 0;
-    return size_t(project_groups(window_pts, kSegGroups)) * size_t(batch) * size_t(nseg) * size_t(nmodes) * elem_of(dtype);
+    return project_workspace_bytes(dtype, window_pts, size_t(batch) * size_t(nseg) * size_t(nmodes), kSegGroups);
 }
 
 int pm_segment_project(int32_t dtype, int32_t source, int64_t rows, int64_t cols, const void* x, const void* y, int64_t nseg, const void* plan,
@@ -327,35 +295,19 @@ int pm_segment_project(int32_t dtype, int32_t source, int64_t rows, int64_t cols
         return rc;
     if (!out || !databar || window_pts < 0 || window_pts > rows * cols)
         return fail(PM_ERR_ARG, "pm_segment_project: bad argument (null out or databar, or window_pts outside [0, rows * cols])");
-    if (batch * nseg * nmodes > INT32_MAX) return fail(PM_ERR_ARG, "pm_segment_project: batch * nseg * nmodes is too large");
-    if (project_lds(1, nmodes, elem_of(dtype)) > kProjectLds)
-        return fail(PM_ERR_UNSUPPORTED, "pm_segment_project: %lld modes do not fit the workgroup's accumulators", (long long)nmodes);
-    if (batch == 0 || nseg == 0 || nmodes == 0) return 0;
-    const size_t need = pm_segment_project_workspace(dtype, window_pts, nseg, nmodes, batch);
-    if (!workspace || workspace_bytes < need)
-        return fail(PM_ERR_WORKSPACE, "pm_segment_project: workspace of %zu bytes is smaller than the %zu pm_segment_project_workspace asks for",
-                    workspace_bytes, need);
-    return by_rdtype(dtype, "pm_segment_project", [&](auto real) {
-        return by_source(source, [&](auto src) {
-            using T = decltype(real);
-            const T *xp = static_cast<const T*>(x), *yp = static_cast<const T*>(y), *mp = static_cast<const T*>(masks);
-            const T *bp = static_cast<const T*>(basis), *g = static_cast<const T*>(databar);
-            const ZStep<T>* steps = static_cast<const ZStep<T>*>(table);
-            T* partial = static_cast<T*>(workspace);
-            hipStream_t st = PM_STREAM(stream);
-            const int64_t groups = project_groups(window_pts, kSegGroups), npts = rows * cols, ld = batch * nseg * nmodes;
-            const dim3 grid{unsigned(groups), unsigned(nseg)}, block{kThreads};
-            for (int64_t b0 = 0; b0 < batch;)
-                b0 += by_nb(batch - b0, project_nb(dtype, nmodes, batch), [&](auto nb) {
-                    hipLaunchKernelGGL((segment_project_kernel<decltype(src)::value, T, decltype(nb)::value>), grid, block,
-                                       project_lds(nb, nmodes, sizeof(T)), st, int(rows), int(cols), xp, yp, int(nseg),
-                                       static_cast<const SegDesc*>(plan), mp, steps, int(nsteps), int(nmodes), bp, g + b0 * npts,
-                                       partial + b0 * nseg * nmodes, ld);
-                });
-            hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(ld)), block, 0, st, groups, ld, partial, static_cast<T*>(out));
-            return int(hipGetLastError());
+    return launch_project(
+        "pm_segment_project", "nseg * nmodes", "modes", dtype, window_pts, nmodes, batch, nseg * nmodes, 0, out, workspace, workspace_bytes, stream,
+        kSegGroups, [&](auto real, auto nb, int64_t b0, int64_t groups, size_t lds, hipStream_t st) {
+            by_source(source, [&](auto src) {
+                using T = decltype(real);
+                hipLaunchKernelGGL((segment_project_kernel<decltype(src)::value, T, decltype(nb)::value>), dim3(unsigned(groups), unsigned(nseg)),
+                                   dim3(kThreads), lds, st, int(rows), int(cols), static_cast<const T*>(x), static_cast<const T*>(y), int(nseg),
+                                   static_cast<const SegDesc*>(plan), static_cast<const T*>(masks), static_cast<const ZStep<T>*>(table),
+                                   int(nsteps), int(nmodes), static_cast<const T*>(basis), static_cast<const T*>(databar) + b0 * rows * cols,
+                                   static_cast<T*>(workspace) + b0 * nseg * nmodes, batch * nseg * nmodes);
+                return 0;
+            });
         });
-    });
 }
 
 }  // extern "C"

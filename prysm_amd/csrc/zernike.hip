@@ -14,6 +14,7 @@
 // The two reductions (project, modes dot) are deterministic: each workgroup reduces its points in a fixed order (lane sums, a
 // butterfly over the wave, waves in LDS slots of their own) and stores one partial per output into the caller's workspace; a second
 // launch sums the partials of each output in a fixed order.  No atomics, so every run and every graph replay gives the same bits.
+// The projection's reduction and its launcher are modal_tile.h's, shared with qpoly.hip, recur.hip and segmented.hip.
 #include "zernike_walk.h"
 
 namespace pm {
@@ -77,65 +78,29 @@ __global__ __launch_bounds__(kThreads) void zernike_sum_kernel(int64_t npts, int
 }
 
 // ---------------------------------------------------------------- projection: one partial per (workgroup, b, k)
-// Each wave sums its 64 x kVec points per step, reduces over its lanes and adds the total into an LDS slot of its own, (wave, b, k);
-// the workgroup adds its waves in order at the end and stores partial[group][b0 + b][k] (row length ld = B * nmodes).  The butterfly
-// reductions of E = 8 / NB consecutive steps run together, 8 independent chains at a time.
+// The reduction of modal_tile.h around walk(): partial[group][b0 + b][k], row length ld = B * nmodes.
 template <typename T, int NB>
 __global__ __launch_bounds__(kThreads) void zernike_project_kernel(int64_t npts, int polar, const T* __restrict__ u, const T* __restrict__ v,
                                                                    const ZStep<T>* __restrict__ table, int nsteps, int nmodes,
                                                                    const T* __restrict__ g, T* __restrict__ partial, int64_t ld, int vec) {
-    constexpr int E = 8 / NB;
     extern __shared__ __align__(16) unsigned char smem[];
-    T* sacc = reinterpret_cast<T*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nacc = NB * nmodes;
-    for (int e = tid; e < kWaves * nacc; e += kThreads) sacc[e] = T(0);
-    __syncthreads();
+    T* sacc = project_begin<T>(smem, nacc, tid);
     T* wacc = sacc + wave * nacc;
-    // the wave stays together through the loop (a shuffle needs every lane) and masks its own tail
     for (int64_t base = wave_tile(wave); base < npts; base += int64_t(gridDim.x) * kThreads * kVec) {
         const bool full = vec && base + 64 * kVec <= npts;
-        T uu[kVec], vv[kVec], gg[NB][kVec], red[NB][E];
-        int slot[E];
+        T uu[kVec], vv[kVec], gg[NB][kVec];
+        ProjectStep<T, NB> step;
         load_pts(u, base, lane, npts, full, uu);
         load_pts(v, base, lane, npts, full, vv);
 #pragma unroll
         for (int b = 0; b < NB; ++b) load_pts(g + int64_t(b) * npts, base, lane, npts, full, gg[b]);
-#pragma unroll
-        for (int j = 0; j < E; ++j) slot[j] = -1;
-        walk<E>(polar != 0, uu, vv, table, nsteps, nmodes,
-                [&](int j, int k, const T z[kVec]) {
-                    slot[j] = k;
-#pragma unroll
-                    for (int b = 0; b < NB; ++b) {
-                        T s = T(0);
-#pragma unroll
-                        for (int q = 0; q < kVec; ++q) s += gg[b][q] * z[q];
-                        red[b][j] = s;
-                    }
-                },
-                [&] {
-#pragma unroll
-                    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-                        for (int j = 0; j < E; ++j)
-#pragma unroll
-                            for (int b = 0; b < NB; ++b) red[b][j] += __shfl_xor(red[b][j], off);
-#pragma unroll
-                    for (int j = 0; j < E; ++j) {
-                        if (slot[j] >= 0 && lane == 0)
-#pragma unroll
-                            for (int b = 0; b < NB; ++b) wacc[b * nmodes + slot[j]] += red[b][j];
-                        slot[j] = -1;
-                    }
-                });
+        step.clear();
+        walk<ProjectStep<T, NB>::E>(polar != 0, uu, vv, table, nsteps, nmodes, [&](int j, int k, const T z[kVec]) { step.emit(j, k, gg, z); },
+                     [&] { step.flush(wacc, nmodes, lane); });
     }
-    __syncthreads();
-    for (int o = tid; o < nacc; o += kThreads) {
-        T s = sacc[o];
-        for (int w = 1; w < kWaves; ++w) s += sacc[w * nacc + o];
-        partial[int64_t(blockIdx.x) * ld + o] = s;
-    }
+    project_end(sacc, nacc, tid, [&](int o, T s) { partial[int64_t(blockIdx.x) * ld + o] = s; });
 }
 
 // ---------------------------------------------------------------- modes dot: partial[chunk][k] = sum over the chunk of modes[k] * g
@@ -236,39 +201,23 @@ int pm_zernike_sum(int32_t dtype, int32_t coords, int64_t npts, const void* u, c
 
 size_t pm_zernike_project_workspace(int32_t dtype, int64_t npts, int64_t nmodes, int64_t batch) {
     if (!real_dtype(dtype) || npts < 0 || nmodes < 0 || batch < 0) return 0;
-    return size_t(project_groups(npts)) * size_t(batch) * size_t(nmodes) * elem_of(dtype);
+    return project_workspace_bytes(dtype, npts, size_t(batch) * size_t(nmodes));
 }
 
 int pm_zernike_project(int32_t dtype, int32_t coords, int64_t npts, const void* u, const void* v, const void* table, int64_t nsteps,
                        int64_t nmodes, int64_t batch, const void* databar, void* out, void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_walk("pm_zernike_project", dtype, coords, npts, u, v, table, nsteps, nmodes)) return rc;
     if (!out || !databar || batch < 0) return fail(PM_ERR_ARG, "pm_zernike_project: bad argument (null pointer or negative batch)");
-    if (batch * nmodes > INT32_MAX) return fail(PM_ERR_ARG, "pm_zernike_project: batch * nmodes is too large");
-    if (project_lds(1, nmodes, elem_of(dtype)) > kProjectLds)
-        return fail(PM_ERR_UNSUPPORTED, "pm_zernike_project: %lld modes do not fit the workgroup's accumulators", (long long)nmodes);
-    if (batch == 0 || nmodes == 0) return 0;
-    const size_t need = pm_zernike_project_workspace(dtype, npts, nmodes, batch);
-    if (!workspace || workspace_bytes < need)
-        return fail(PM_ERR_WORKSPACE, "pm_zernike_project: workspace of %zu bytes is smaller than the %zu pm_zernike_project_workspace asks for",
-                    workspace_bytes, need);
-    return by_rdtype(dtype, "pm_zernike_project", [&](auto real) {
-        using T = decltype(real);
-        const T *up = static_cast<const T*>(u), *vp = static_cast<const T*>(v), *g = static_cast<const T*>(databar);
-        const ZStep<T>* steps = static_cast<const ZStep<T>*>(table);
-        T* partial = static_cast<T*>(workspace);
-        hipStream_t st = PM_STREAM(stream);
-        const int64_t groups = project_groups(npts), nout = batch * nmodes;
-        const dim3 grid{unsigned(groups)}, block{kThreads};
-        const int vec = vec_ok(npts, {u, v, databar});
-        for (int64_t b0 = 0; b0 < batch;)
-            b0 += by_nb(batch - b0, project_nb(dtype, nmodes, batch), [&](auto nb) {
-                hipLaunchKernelGGL((zernike_project_kernel<T, decltype(nb)::value>), grid, block, project_lds(nb, nmodes, sizeof(T)), st, npts,
-                                   coords == PM_ZERNIKE_POLAR, up, vp, steps, int(nsteps), int(nmodes), g + b0 * npts, partial + b0 * nmodes,
-                                   nout, vec);
-            });
-        hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(nout)), block, 0, st, groups, nout, partial, static_cast<T*>(out));
-        return int(hipGetLastError());
-    });
+    const int vec = vec_ok(npts, {u, v, databar});
+    return launch_project("pm_zernike_project", "nmodes", "modes", dtype, npts, nmodes, batch, nmodes, 0, out, workspace, workspace_bytes, stream,
+                          kMaxProjectGroups, [&](auto real, auto nb, int64_t b0, int64_t groups, size_t lds, hipStream_t st) {
+                              using T = decltype(real);
+                              hipLaunchKernelGGL((zernike_project_kernel<T, decltype(nb)::value>), dim3(unsigned(groups)), dim3(kThreads), lds, st,
+                                                 npts, coords == PM_ZERNIKE_POLAR, static_cast<const T*>(u), static_cast<const T*>(v),
+                                                 static_cast<const ZStep<T>*>(table), int(nsteps), int(nmodes),
+                                                 static_cast<const T*>(databar) + b0 * npts, static_cast<T*>(workspace) + b0 * nmodes,
+                                                 batch * nmodes, vec);
+                          });
 }
 
 size_t pm_modes_dot_workspace(int32_t dtype, int64_t nmodes, int64_t npts) {
@@ -296,7 +245,8 @@ int pm_modes_dot(int32_t dtype, int64_t nmodes, int64_t npts, const void* modes,
         const int vec = vec_ok(npts, {modes, v}) && mode_stride % kVec == 0;
         hipLaunchKernelGGL(modes_dot_kernel<T>, grid, block, 0, st, npts, int(nmodes), static_cast<const T*>(modes), mode_stride,
                            static_cast<const T*>(v), partial, vec);
-        hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(nmodes)), block, 0, st, chunks, nmodes, partial, static_cast<T*>(out));
+        hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(unsigned(nmodes)), block, 0, st, chunks, nmodes, partial, 0,
+                           static_cast<T*>(out));
         return int(hipGetLastError());
     });
 }

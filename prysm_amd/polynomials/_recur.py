@@ -8,28 +8,16 @@ import torch
 
 from .. import _lib as L
 from . import recur_plan as RP
-from .zernike import _dtype_of, _code
+from ._modal import _dtype_of, _code, _cached, _device_table, _check_coefs, _check_bar, _projector
 
 _TABLES = {}
 _TABLES_MAX = 128
 _PAIRS = {}
 
 
-def _cached(cache, key, make):
-    hit = cache.get(key)
-    if hit is None:
-        if len(cache) >= _TABLES_MAX:
-            cache.pop(next(iter(cache)))
-        hit = cache[key] = make()
-    return hit
-
-
 def _table(family, params, ns, nmax, dt):
     """the table of (family, params, orders, dtype) on the current device: (uint8 device tensor, number of records)"""
-    def make():
-        t = RP.plan(family, ns, *params, nmax=nmax, dtype=np.float32 if dt == torch.float32 else np.float64)
-        return torch.from_numpy(t.view(np.uint8).copy()).to(L.device()), len(t)
-    return _cached(_TABLES, (family, params, ns, nmax, dt, L._cur_dev()), make)
+    return _device_table(_TABLES, _TABLES_MAX, (family, params, ns, nmax), dt, lambda npdt: RP.plan(family, ns, *params, nmax=nmax, dtype=npdt))
 
 
 def _params(family, params):
@@ -95,12 +83,7 @@ def make_family(family, where):
 
 def _coefs(coefs, K, what='coefficients'):
     """(coefs as given, single): checked for shape (K,) or (B, K) and a real dtype"""
-    if not isinstance(coefs, torch.Tensor):
-        coefs = np.asarray(coefs)
-    shape = tuple(coefs.shape)
-    if len(shape) not in (1, 2) or shape[-1] != K:
-        raise ValueError(f'{what} of shape {shape} do not match the {K} orders given (want ({K},) or (B, {K}))')
-    _dtype_of(coefs, what)
+    coefs, shape = _check_coefs(coefs, K, what, 'orders')
     return coefs, len(shape) == 1
 
 
@@ -143,11 +126,7 @@ def sum1d(family, params, coefs, ns, x, y=None, radius=None, want='z'):
 
 def _bar(g, shape, what):
     """(g as given, is a single map): g of the coordinates' shape or a (B, ...) stack of them, real"""
-    sg = tuple(g.shape) if isinstance(g, torch.Tensor) else tuple(np.shape(g))
-    if sg != shape and sg[1:] != shape:
-        raise ValueError(f'{what} of shape {sg} does not match coordinates of shape {shape} (or a (B, ...) stack of them)')
-    _dtype_of(g, what)
-    return g, sg == shape
+    return g, _check_bar(g, shape, what) == shape
 
 
 def project1d(family, params, ns, x, y=None, radius=None, databar=None, dx_bar=None, dy_bar=None):
@@ -170,13 +149,11 @@ def project1d(family, params, ns, x, y=None, radius=None, databar=None, dx_bar=N
     B = 1 if single else first.shape[0]
     out = torch.zeros((B, len(ns)), dtype=dt, device=x.device)
     if len(ns) and B and x.numel():
-        lib = L.load()
         tab, nsteps = _table(family, params, ns, None, dt)
-        ws = L.workspace(lib.pm_recur_project_workspace(_code(dt), x.numel(), len(ns), B))
+        project = _projector('recur', dt, x.numel(), len(ns), B)
 
         def run(der, a, b):
-            L.check(lib.pm_recur_project(_code(dt), form, x.numel(), L.ptr(x), L.ptr(y), radius, L.ptr(tab), nsteps, len(ns), B, der,
-                                         L.ptr(a), L.ptr(b), 1, L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr()))
+            project(form, x.numel(), L.ptr(x), L.ptr(y), radius, L.ptr(tab), nsteps, len(ns), B, der, L.ptr(a), L.ptr(b), 1, L.ptr(out))
         if g is not None:
             run(0, g, None)
         if form == L.PM_RECUR_X:
@@ -234,7 +211,7 @@ def _flat_index(mns, nx):
     def make():
         idx = [n * nx + m for m, n in mns]
         return torch.tensor(idx, dtype=torch.int64, device=L.device()), len(set(idx)) != len(idx)
-    return _cached(_PAIRS, ('flat', mns, nx, L._cur_dev()), make)
+    return _cached(_PAIRS, _TABLES_MAX, ('flat', mns, nx, L._cur_dev()), make)
 
 
 def sum2d(family, coefs, mns, x, y, want='z', x_norm=1.0, y_norm=1.0, cartesian_grid=True):
@@ -314,7 +291,8 @@ def outer_seq(mns, x, y, xder, yder, cartesian_grid=True):
     nx, ny = max(m for m, _ in mns) + 1, max(n for _, n in mns) + 1
     tx = basis('monomial', (), range(nx), getx(), 'd' if xder else 'p')
     ty = basis('monomial', (), range(ny), gety(), 'd' if yder else 'p')
-    pairs = _cached(_PAIRS, ('pairs', mns, L._cur_dev()), lambda: torch.tensor(mns, dtype=torch.int32, device=L.device()).contiguous())
+    pairs = _cached(_PAIRS, _TABLES_MAX, ('pairs', mns, L._cur_dev()),
+                    lambda: torch.tensor(mns, dtype=torch.int32, device=L.device()).contiguous())
     L.check(L.load().pm_recur2_outer(_code(dt), rows, cols, len(mns), L.ptr(ty), ny, L.ptr(tx), nx, L.ptr(pairs), L.ptr(out),
                                      L.stream_ptr()))
     return out

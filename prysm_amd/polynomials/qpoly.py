@@ -12,7 +12,7 @@ import torch
 from .. import _lib as L
 from .qpoly_plan import (g_qbfs, h_qbfs, f_qbfs, abc_q2d, G_q2d, F_q2d, g_q2d, f_q2d, Q2d_nm_c_to_a_b,  # noqa: F401
                          check_ns, check_q2d_nms, plan, QBFS, QCON, Q2D)
-from .zernike import _dtype_of, _code
+from ._modal import _dtype_of, _code, _device_table, _check_coefs, _check_bar, _projector
 
 __all__ = ['g_qbfs', 'h_qbfs', 'f_qbfs', 'abc_q2d', 'G_q2d', 'F_q2d', 'g_q2d', 'f_q2d', 'Q2d_nm_c_to_a_b', 'Qbfs', 'Qbfs_seq',
            'Qcon', 'Qcon_seq', 'Q2d', 'Q2d_seq', 'compute_z_Qbfs', 'compute_z_Q2d', 'Q2d_sum', 'Q2d_sum_adjoint', 'Qcon_sum',
@@ -24,14 +24,7 @@ _TABLES_MAX = 64
 
 def _table(modes, family, dtype):
     """the step table of (modes, family, dtype) on the current device: (uint8 device tensor, number of steps)"""
-    key = (modes, family, dtype, L._cur_dev())
-    hit = _TABLES.get(key)
-    if hit is None:
-        t = plan(modes, family, np.float32 if dtype == torch.float32 else np.float64)
-        if len(_TABLES) >= _TABLES_MAX:
-            _TABLES.pop(next(iter(_TABLES)))
-        hit = _TABLES[key] = (torch.from_numpy(t.view(np.uint8).copy()).to(L.device()), len(t))
-    return hit
+    return _device_table(_TABLES, _TABLES_MAX, (modes, family), dtype, lambda npdt: plan(modes, family, npdt))
 
 
 def _modes(modes, family):
@@ -65,12 +58,7 @@ def _seq(modes, family, u, v, coords):
 
 def _sum(coefs, modes, family, u, v, coords):
     modes = _modes(modes, family)
-    if not isinstance(coefs, torch.Tensor):
-        coefs = np.asarray(coefs)
-    shape = tuple(coefs.shape)
-    if len(shape) not in (1, 2) or shape[-1] != len(modes):
-        raise ValueError(f'coefs of shape {shape} do not match the {len(modes)} modes given (want ({len(modes)},) or (B, {len(modes)}))')
-    _dtype_of(coefs, 'Q polynomial coefficients')
+    coefs, shape = _check_coefs(coefs, len(modes), 'coefs', 'modes', 'Q polynomial coefficients')
     u, v, dt, ushape = _points(u, v)
     single = len(shape) == 1
     B = 1 if single else shape[0]
@@ -90,21 +78,16 @@ def _adjoint(databar, modes, family, u, v, coords):
     shape_u = tuple(np.shape(u))
     if v is not None and tuple(np.shape(v)) != shape_u:
         raise ValueError(f'coordinate arrays differ in shape: {shape_u} and {tuple(np.shape(v))}')
-    shape_g = tuple(databar.shape) if isinstance(databar, torch.Tensor) else np.shape(databar)
-    if shape_g != shape_u and shape_g[1:] != shape_u:
-        raise ValueError(f'databar of shape {shape_g} does not match coordinates of shape {shape_u} (or a (B, ...) stack of them)')
-    _dtype_of(databar, 'databar')
+    shape_g = _check_bar(databar, shape_u, 'databar')
     u, v, dt, ushape = _points(u, v)
     single = shape_g == ushape
     g = L.as_device(databar, dt)
     B = 1 if single else shape_g[0]
     out = torch.empty((B, len(modes)), dtype=dt, device=u.device)
     if len(modes) and B:
-        lib = L.load()
         tab, nsteps = _table(modes, family, dt)
-        ws = L.workspace(lib.pm_qpoly_project_workspace(_code(dt), u.numel(), len(modes), B))
-        L.check(lib.pm_qpoly_project(_code(dt), coords, u.numel(), L.ptr(u), L.ptr(v), L.ptr(tab), nsteps, len(modes), B, L.ptr(g),
-                                     L.ptr(out), L.ptr(ws), ws.numel() if ws is not None else 0, L.stream_ptr()))
+        _projector('qpoly', dt, u.numel(), len(modes), B)(coords, u.numel(), L.ptr(u), L.ptr(v), L.ptr(tab), nsteps, len(modes), B, L.ptr(g),
+                                                          L.ptr(out))
     return out[0] if single else out
 
 

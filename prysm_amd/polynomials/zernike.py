@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ._modal import _dtype_of, _code, _device_table, _check_coefs, _check_bar, _projector
 from .zernike_plan import (zernike_norm, noll_to_nm, fringe_to_nm, nm_to_fringe, nm_to_ansi_j, ansi_j_to_nm, check_nms,  # noqa: F401
                            plan)
 
@@ -21,26 +22,7 @@ _TABLES_MAX = 64
 
 def _table(nms, norm, dtype):
     """the step table of (nms, norm, dtype) on the current device: (uint8 device tensor, number of steps)"""
-    key = (nms, bool(norm), dtype, L._cur_dev())
-    hit = _TABLES.get(key)
-    if hit is None:
-        t = plan(nms, norm, np.float32 if dtype == torch.float32 else np.float64)
-        if len(_TABLES) >= _TABLES_MAX:
-            _TABLES.pop(next(iter(_TABLES)))
-        hit = _TABLES[key] = (torch.from_numpy(t.view(np.uint8).copy()).to(L.device()), len(t))
-    return hit
-
-
-def _dtype_of(a, what='Zernike coordinates'):
-    """float32 for float32 input, float64 for any other real input; TypeError for complex"""
-    if isinstance(a, torch.Tensor):
-        if a.is_complex():
-            raise TypeError(f'{what} must be real')
-        return torch.float32 if a.dtype == torch.float32 else torch.float64
-    dt = np.asarray(a).dtype
-    if np.issubdtype(dt, np.complexfloating):
-        raise TypeError(f'{what} must be real')
-    return torch.float32 if dt == np.float32 else torch.float64
+    return _device_table(_TABLES, _TABLES_MAX, (nms, bool(norm)), dtype, lambda npdt: plan(nms, norm, npdt))
 
 
 def _coords(u, v):
@@ -52,10 +34,6 @@ def _coords(u, v):
     du, dv = _dtype_of(u), _dtype_of(v)
     dt = torch.float32 if du == dv == torch.float32 else torch.float64
     return L.as_device(u, dt), L.as_device(v, dt), dt, su
-
-
-def _code(dt):
-    return L.PM_F32 if dt == torch.float32 else L.PM_F64
 
 
 # _seq, _sum and _adjoint take either coordinate form: coords PM_ZERNIKE_POLAR reads (u, v) as (r, t), PM_ZERNIKE_CARTESIAN as (x, y)
@@ -90,12 +68,7 @@ def zernike_sum(coefs, nms, x, y, norm=True):
 
 def _sum(coefs, nms, x, y, norm, coords):
     nms = check_nms(nms)
-    if not isinstance(coefs, torch.Tensor):
-        coefs = np.asarray(coefs)
-    shape = tuple(coefs.shape)
-    if len(shape) not in (1, 2) or shape[-1] != len(nms):
-        raise ValueError(f'coefs of shape {shape} do not match the {len(nms)} modes given (want ({len(nms)},) or (B, {len(nms)}))')
-    _dtype_of(coefs, 'Zernike coefficients')
+    coefs, shape = _check_coefs(coefs, len(nms), 'coefs', 'modes', 'Zernike coefficients')
     x, y, dt, xshape = _coords(x, y)
     c = L.as_device(coefs, dt).reshape(-1, len(nms))
     single, B = len(shape) == 1, c.shape[0]
@@ -119,21 +92,16 @@ def zernike_sum_adjoint(databar, nms, x, y, norm=True):
 def _adjoint(databar, nms, x, y, norm, coords):
     nms = check_nms(nms)
     shape_x, shape_y = tuple(np.shape(x)), tuple(np.shape(y))
-    shape_g = tuple(databar.shape) if isinstance(databar, torch.Tensor) else np.shape(databar)
     if shape_x != shape_y:
         raise ValueError(f'coordinate arrays differ in shape: {shape_x} and {shape_y}')
-    if shape_g != shape_x and shape_g[1:] != shape_x:
-        raise ValueError(f'databar of shape {shape_g} does not match coordinates of shape {shape_x} (or a (B, ...) stack of them)')
-    _dtype_of(databar, 'databar')
+    shape_g = _check_bar(databar, shape_x, 'databar')
     x, y, dt, xshape = _coords(x, y)
     single = shape_g == xshape
     g = L.as_device(databar, dt)
     B = 1 if single else shape_g[0]
     out = torch.empty((B, len(nms)), dtype=dt, device=x.device)
     if len(nms) and B:
-        lib = L.load()
         tab, nsteps = _table(nms, norm, dt)
-        ws = L.workspace(lib.pm_zernike_project_workspace(_code(dt), x.numel(), len(nms), B))
-        L.check(lib.pm_zernike_project(_code(dt), coords, x.numel(), L.ptr(x), L.ptr(y), L.ptr(tab), nsteps, len(nms), B,
-                                       L.ptr(g), L.ptr(out), L.ptr(ws), ws.numel() if ws is not None else 0, L.stream_ptr()))
+        _projector('zernike', dt, x.numel(), len(nms), B)(coords, x.numel(), L.ptr(x), L.ptr(y), L.ptr(tab), nsteps, len(nms), B, L.ptr(g),
+                                                          L.ptr(out))
     return out[0] if single else out

@@ -512,13 +512,11 @@ class CompositeHexagonalAperture:
         out = torch.empty((B, S, K), dtype=self.dtype, device=L.device())
         if S and K and B:
             d, kind, K, basis = self._args()
-            lib = L.load()
-            code = L.PM_F32 if self.dtype == torch.float32 else L.PM_F64
+            from .polynomials._modal import _projector
             wpts = self._route['plan'].window_pts
-            ws = L.workspace(lib.pm_segment_project_workspace(code, wpts, S, K, B))
-            L.check(lib.pm_segment_project(code, kind, rows, cols, L.ptr(d['x']), L.ptr(d['y']), S, L.ptr(d['desc']), L.ptr(d['masks']), wpts,
-                                           L.ptr(d['table']), d['nsteps'], K, L.ptr(basis), B, L.ptr(g), L.ptr(out), L.ptr(ws),
-                                           ws.numel() if ws is not None else 0, L.stream_ptr()))
+            _projector('segment', self.dtype, wpts, S, K, B)(kind, rows, cols, L.ptr(d['x']), L.ptr(d['y']), S, L.ptr(d['desc']),
+                                                             L.ptr(d['masks']), wpts, L.ptr(d['table']), d['nsteps'], K, L.ptr(basis), B,
+                                                             L.ptr(g), L.ptr(out))
         elif B:
             out.zero_()
         return out[0] if single else out

@@ -118,6 +118,29 @@ def test_a_stack_of_11_equals_single_calls(dt):
         assert _rel(A[b], tonp(P.jacobi_radial_sum_adjoint(G[b], ns, 0.0, 2.0, x, y, 1.1, dx_bar=G[10 - b]))) < tol
 
 
+@pytest.mark.parametrize('dt', [np.float64, np.float32])
+@pytest.mark.parametrize('npts', [1024, 1027])
+def test_a_stack_of_15_equals_single_calls(dt, npts):
+    """15 = 8 + 4 + 2 + 1 vectors per walk (the stack of 11 never takes the pieces of 4), each piece at its own offset into the
+    coefficients, the outputs, the three adjoint inputs and the partials; 1024 points take the 16-byte path, 1027 the element-wise one"""
+    from prysm_amd import polynomials as P
+    rng = np.random.default_rng(15)
+    x, y = (rng.uniform(-0.7, 0.7, npts).astype(dt) for _ in range(2))
+    ns = [0, 1, 2, 4, 7, 9]
+    C = rng.standard_normal((15, len(ns))).astype(dt)
+    S = [tonp(a) for a in P.jacobi_radial_sum_der_xy(C, ns, 0.0, 2.0, x, y, 1.1)]
+    tol = 1e-14 if dt == np.float64 else 1e-6
+    for b in range(15):
+        one = [tonp(a) for a in P.jacobi_radial_sum_der_xy(C[b], ns, 0.0, 2.0, x, y, 1.1)]
+        for s, o in zip(S, one):
+            assert s.shape == (15, npts) and s.dtype == dt and _rel(s[b], o) < tol
+    G, GX, GY = (rng.standard_normal((15, npts)).astype(dt) for _ in range(3))
+    A = tonp(P.jacobi_radial_sum_adjoint(G, ns, 0.0, 2.0, x, y, 1.1, dx_bar=GX, dy_bar=GY))
+    assert A.shape == (15, len(ns)) and A.dtype == dt
+    for b in range(15):
+        assert _rel(A[b], tonp(P.jacobi_radial_sum_adjoint(G[b], ns, 0.0, 2.0, x, y, 1.1, dx_bar=GX[b], dy_bar=GY[b]))) < tol
+
+
 def test_1d_project_against_the_numpy_walk_and_the_dot_product_identity():
     from prysm_amd import polynomials as P
     from prysm_amd.polynomials import _recur as R
