@@ -3,6 +3,13 @@
 
 using namespace pm;
 
+// the chirp-Z launchers answer -2 when no kernel was built for a length
+static int no_czt_kernel(int rc, const char* what, int64_t K) {
+    return rc == -2 ? fail(PM_ERR_UNSUPPORTED, "%s: no kernel for K = %lld", what, (long long)K) : rc;
+}
+// base addresses of real arrays that are read as pairs
+static bool complex_aligned(const pm_fft2_desc* d, const void* p) { return reinterpret_cast<uintptr_t>(p) % elem_size(d->dtype) == 0; }
+
 extern "C" {
 
 int pm_fft2(const pm_fft2_desc* d, const void* in, void* out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -10,12 +17,12 @@ int pm_fft2(const pm_fft2_desc* d, const void* in, void* out, void* workspace, s
     if (rc) return rc;
     if (!in || !out) return fail(PM_ERR_ARG, "pm_fft2: null buffer");
     Fft2Plan p = plan_fft2(d);
-    if (p.r2c && reinterpret_cast<uintptr_t>(in) % (d->dtype == PM_C64 ? 8 : 16) != 0) {
+    if (p.r2c && !complex_aligned(d, in)) {
         // the Hermitian path reads the real array as pairs; the complex path that takes over has neither the centre normalisation nor
         // the |.| / angle epilogues (check_fft2 accepted them on the strength of r2c_legal): refuse, do not run something else
         if ((d->flags & PM_FLAG_NORM_DC) || d->epilogue == PM_EPI_ABS || d->epilogue == PM_EPI_ARG)
             return fail(PM_ERR_UNSUPPORTED, "pm_fft2: PM_FLAG_NORM_DC / PM_EPI_ABS / PM_EPI_ARG read the real array as pairs; its base address "
-                        "must be aligned like a complex element (%d bytes)", d->dtype == PM_C64 ? 8 : 16);
+                        "must be aligned like a complex element (%d bytes)", int(elem_size(d->dtype)));
         p = plan_fft2(d, false);
     }
     if (!workspace || workspace_bytes < p.ws_bytes)
@@ -54,7 +61,7 @@ int pm_fft2_spectral(const pm_fft2_desc* d, int32_t count, const double* k, cons
     for (int32_t b0 = 0; b0 < count; b0 += g) {
         Spectral w{};
         w.nb = count - b0 < g ? count - b0 : g;
-        w.fstride = int64_t(p.ws_field / (d->dtype == PM_C64 ? sizeof(cx<float>) : sizeof(cx<double>)));
+        w.fstride = p.wstride;
         for (int i = 0; i < w.nb; ++i) {
             w.w[i] = weight[b0 + i];
             w.k2[i] = k[b0 + i] / two_pi;
@@ -78,7 +85,7 @@ int pm_fft2_mul_ifft2(const pm_fft2_desc* d, const void* in, void* out, void* wo
             return fail(PM_ERR_UNSUPPORTED, "pm_fft2_mul_ifft2: PM_FLAG_REAL_OUTPUT needs a real unpadded power-of-two field (rows of 64 .. 8192 "
                         "samples), a full multiplier, x rotations by 0 or N/2 and an unwindowed output; take the real part of the complex "
                         "chain instead");
-        if (reinterpret_cast<uintptr_t>(in) % (d->dtype == PM_C64 ? 8 : 16) != 0 || reinterpret_cast<uintptr_t>(out) % (d->dtype == PM_C64 ? 8 : 16) != 0)
+        if (!complex_aligned(d, in) || !complex_aligned(d, out))
             return fail(PM_ERR_UNSUPPORTED, "pm_fft2_mul_ifft2: PM_FLAG_REAL_OUTPUT reads and writes the real arrays as pairs; their base "
                         "addresses must be aligned like a complex element (take the real part of the complex chain instead)");
         if (!workspace || workspace_bytes < hp.ws_bytes)
@@ -92,9 +99,8 @@ int pm_fft2_mul_ifft2(const pm_fft2_desc* d, const void* in, void* out, void* wo
         return fail(PM_ERR_UNSUPPORTED, "pm_fft2_mul_ifft2: takes powers of two <= 8192 on both axes, or (one field, complex output) a composite "
                     "column length with primes <= 19 beside a row length of either kind (got %lld x %lld); compose two pm_fft2 calls instead",
                     (long long)d->in_y.n, (long long)d->in_x.n);
-    const size_t need = p.ws_bytes;
-    if (!workspace || workspace_bytes < need)
-        return fail(PM_ERR_WORKSPACE, "pm_fft2_mul_ifft2: workspace of %zu bytes required, %zu given", need, workspace_bytes);
+    if (!workspace || workspace_bytes < p.ws_bytes)
+        return fail(PM_ERR_WORKSPACE, "pm_fft2_mul_ifft2: workspace of %zu bytes required, %zu given", p.ws_bytes, workspace_bytes);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (d->dtype == PM_C64) return fused_run<float>(d, p, in, out, workspace, st);
     return fused_run<double>(d, p, in, out, workspace, st);
@@ -158,7 +164,7 @@ int pm_czt_axis(int32_t dtype, int32_t axis, int64_t nseq, int64_t K, int64_t in
                                        in_ld, out, out_ld, st)
                  : czt_axis_run<double>(axis, nseq, K, in_len, in_off, out_len, out_off, pre, pre_conj, H, h_conj, post, post_conj, scale,
                                         in, in_ld, out, out_ld, st);
-    return rc == -2 ? fail(PM_ERR_UNSUPPORTED, "pm_czt_axis: no kernel for K = %lld", (long long)K) : rc;
+    return no_czt_kernel(rc, "pm_czt_axis", K);
 }
 
 int pm_fft1_ramp(int32_t dtype, int32_t direction, int32_t axis, int64_t nseq, int64_t K, int64_t in_len, int64_t in_off, int64_t out_len,
@@ -181,7 +187,7 @@ int pm_fft1_ramp(int32_t dtype, int32_t direction, int32_t axis, int64_t nseq, i
                                        in_ld, out, out_ld, st, single)
                  : czt_axis_run<double>(axis, nseq, K, in_len, in_off, out_len, out_off, pre, pre_conj, nullptr, 0, post, post_conj, scale,
                                         in, in_ld, out, out_ld, st, single);
-    return rc == -2 ? fail(PM_ERR_UNSUPPORTED, "pm_fft1_ramp: no kernel for K = %lld", (long long)K) : rc;
+    return no_czt_kernel(rc, "pm_fft1_ramp", K);
 }
 
 int pm_fft1(int32_t dtype, int32_t direction, int32_t axis, int64_t batch, const pm_axis* t_in, const pm_axis* t_out,

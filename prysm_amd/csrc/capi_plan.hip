@@ -10,9 +10,6 @@ static int sibling_log_g(int log_k) {
     return log_k < 1 ? 1 : (log_k > 3 ? 3 : log_k);
 }
 
-// log2 of a power of two (the layout tile tc << log_k); 0 for 0
-static int log2_pow2(int64_t v) { int l = 0; while ((int64_t(1) << l) < v) ++l; return l; }
-
 // layout tile width TL = tc << log_k, auto: >= 256 B pieces from 4096 columns
 static int auto_log_k(int64_t N) { return N >= 8192 ? 3 : (N >= 4096 ? 2 : 1); }
 
@@ -25,7 +22,7 @@ static int nt_in_for(size_t in_bytes) { return tuning().nt_in >= 0 ? tuning().nt
 // 256 MiB (4096^2 complex128), -10 % at 512 MiB and 1 GiB (8192^2), -8 % at 128 MiB.  logm_tile: log2 of the column tile, -1 = the output's.
 static int col_store_nt(const pm_fft2_desc* d, int logm_tile) {
     if (tuning().nt_out >= 0) return tuning().nt_out;
-    const size_t oes = (d->dtype == PM_C64 ? 8 : 16) / (d->epilogue == PM_EPI_NONE ? 1 : 2);
+    const size_t oes = elem_size(d->dtype) / (d->epilogue == PM_EPI_NONE ? 1 : 2);
     const size_t out_bytes = size_t(d->batch > 1 ? d->batch : 1) * size_t(d->out_y.len) * size_t(d->out_x.len) * oes;
     if (logm_tile < 0) logm_tile = engine_log2(d->out_y.n) >= 0 ? engine_log2(d->out_y.n) : 12;
     const size_t piece = size_t(col_tile_width_for(d->dtype, logm_tile, 0)) * oes;
@@ -110,19 +107,16 @@ int64_t batch_chunk(int64_t nb, size_t ws_field) {
 }
 
 Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
-    Fft2Plan p;
+    Fft2Plan p{};
     const int64_t M = d->in_y.n, N = d->in_x.n;
     p.logn = engine_log2(N);
     p.logm = engine_log2(M);
-    const size_t es = d->dtype == PM_C64 ? 8 : 16;
+    const size_t es = elem_size(d->dtype);
     const int64_t rows = d->in_y.len;   // only stored input rows are transformed in pass 1
-    p.fold = false;
     p.w_ld = N;
-    p.hermt_row_var = 0;
     p.r2c = allow_r2c && p.logn >= 0 && p.logm >= 0 && r2c_legal(d, p.logn, p.logm);
     p.r2c_t = p.r2c && hermt_legal(d, p.logn, p.logm);
     if (p.r2c_t) {
-        p.col_var = p.tc = p.log_k = 0;
         p.ws_bytes = size_t(M / 2) * size_t(N) * es;      // rows u < M/2 of the column spectra, row-major (row 0 carries u = 0 and u = M/2)
         p.fold = hermt_fold(p.logm);
         p.hermt_row_var = tuning().herm_t_rowvar == 0 ? 0 : 4;      // knob herm_t_rowvar; default: the complex path's tiling (fft_kernels.h built_row_var)
@@ -133,50 +127,42 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
         p.col_log_g = tuning().col_log_g >= 0 ? tuning().col_log_g : (p.logm >= 12 ? 4 : 0);
         while (p.col_log_g > 0 && ((p.fold ? 2 * tiles : tiles) % (8 << (p.col_log_g + (p.fold ? 1 : 0)))) != 0) --p.col_log_g;
     } else if (p.r2c) {
-        p.col_var = 0;
-        p.tc = col_tile_width_for(d->dtype, p.logm, 0);
-        // layout tiles of 8 column tiles: mtf_from_psf 4096^2 fp32 73.6 -> 72.0 us against 4 (profiles/r05/exp_layout_sweep.log)
-        p.log_k = tuning().log_k >= 0 ? tuning().log_k : 3;
+        int tc = col_tile_width_for(d->dtype, p.logm, 0);
         // fold (one radix-2 step of the column transform in the row pass, as in the complex path): half-length column tiles, two
         // workgroups per CU whose load / transform / store phases overlap -- here from 1024-point columns, because the Hermitian
         // column pass has only half the tiles to fill the chip with
         const int f = tuning().fold;
         p.fold = (f > 0 || (f < 0 && p.logm >= 10)) && p.logm >= 5 && (d->in_y.shift == 0 || d->in_y.shift == M / 2) &&
                  (d->out_y.shift == 0 || d->out_y.shift == M / 2);
-        if (p.fold) p.tc = col_tile_width_for(d->dtype, p.logm - 1, 0);
+        if (p.fold) tc = col_tile_width_for(d->dtype, p.logm - 1, 0);
         const int tlog = p.fold ? p.logm - 1 : p.logm;
         if (tuning().herm_wide && tlog == 11 && (N / 2) % col_tile_width_for(d->dtype, 11, 2) == 0) {
             p.col_var = 2;
-            p.tc = col_tile_width_for(d->dtype, 11, 2);
+            tc = col_tile_width_for(d->dtype, 11, 2);
         }
-        while (p.log_k > 0 && ((N / 2) % (int64_t(p.tc) << p.log_k)) != 0) --p.log_k;
-        const int64_t nc = N / 2, tl = int64_t(p.tc) << p.log_k;
-        p.ws_bytes = size_t((nc + tl - 1) / tl) * size_t(M) * size_t(tl) * es;
-        p.col_log_g = sibling_log_g(p.log_k);
+        // layout tiles of 8 column tiles: mtf_from_psf 4096^2 fp32 73.6 -> 72.0 us against 4 (profiles/r05/exp_layout_sweep.log)
+        p.lay = TiledLayout::make(tc, tuning().log_k >= 0 ? tuning().log_k : 3, N / 2, M, p.fold);
+        p.ws_bytes = p.lay.bytes(es);
+        p.col_log_g = sibling_log_g(p.lay.log_k);
         // folded: several rounds of one-workgroup-per-CU tiles (8192^2: 1024 of them): ALL 32 workgroups an XCD holds take adjacent tiles,
         // so a row of the output is written 2 KiB at a time -- mtf_from_psf 8192^2 fp32 391 -> 373 us (exp_layout_sweep.log)
-        const int ntiles = int((nc + p.tc - 1) / p.tc);
+        const int ntiles = p.lay.ntiles();
         if (p.fold && tuning().col_log_g < 0 && 2 * ntiles > 2 * pm_num_cus())
             for (p.col_log_g = 5; p.col_log_g > 3 && ntiles % (8 << p.col_log_g); --p.col_log_g) {}
     } else if (p.logn >= 0 && p.logm >= 0) {
         p.fold = fold_legal(d, p.logn, p.logm) && fold_auto(p.logm);
-        {   // 128 B tiles exist for 2048-point complex128 tiles only (fft_kernels.h launch_fft): the knob can switch them off or, for an
-            // unfolded 2048-row transform, on -- nothing else
-            const bool want2 = tuning().col_var >= 0 ? tuning().col_var == 2 : (p.fold && p.logm == 12);
-            p.col_var = (want2 && d->dtype == PM_C128 && (p.fold ? p.logm - 1 : p.logm) == 11) ? 2 : 0;
-        }
-        p.tc = col_tile_width_for(d->dtype, p.fold ? p.logm - 1 : p.logm, p.col_var);
-        p.log_k = tuning().log_k >= 0 ? tuning().log_k : auto_log_k(N);
+        // 128 B tiles exist for 2048-point complex128 tiles only (fft_kernels.h launch_fft): the knob can switch them off or, for an
+        // unfolded 2048-row transform, on -- nothing else
+        const bool want2 = tuning().col_var >= 0 ? tuning().col_var == 2 : (p.fold && p.logm == 12);
+        p.col_var = (want2 && d->dtype == PM_C128 && (p.fold ? p.logm - 1 : p.logm) == 11) ? 2 : 0;
+        int log_k = tuning().log_k >= 0 ? tuning().log_k : auto_log_k(N);
         // folded 4096^2 complex64 (intermediate = 128 MiB, inside the Infinity Cache): 8 KiB row pieces measured 95.0 vs 97.8 us
         // (profiles/r01/tune_log_k.log); every other size / precision measured best with the narrow tiles above
-        if (tuning().log_k < 0 && p.fold && d->dtype == PM_C64 && N == 4096 && M == 4096) p.log_k = 7;
-        while (p.log_k > 0 && (N % (int64_t(p.tc) << p.log_k)) != 0) --p.log_k;
-        const int64_t tl = int64_t(p.tc) << p.log_k;
-        const int64_t ntl = (N + tl - 1) / tl;
-        p.ws_bytes = size_t(ntl) * size_t(rows) * size_t(tl) * es;
-        p.col_log_g = sibling_log_g(p.log_k);
+        if (tuning().log_k < 0 && p.fold && d->dtype == PM_C64 && N == 4096 && M == 4096) log_k = 7;
+        p.lay = TiledLayout::make(col_tile_width_for(d->dtype, p.fold ? p.logm - 1 : p.logm, p.col_var), log_k, N, rows, p.fold);     // (a fold stores every row)
+        p.ws_bytes = p.lay.bytes(es);
+        p.col_log_g = sibling_log_g(p.lay.log_k);
     } else {
-        p.tc = p.log_k = 0;
         p.col_log_g = 1;    // (the natural column pass's, when the columns are engine lengths)
         if (p.logm < 0 && use_mix(M)) {
             const int64_t line = int64_t(128 / es);
@@ -186,10 +172,10 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
     }
     if (p.ws_bytes == 0) p.ws_bytes = es;
     p.nbatch = d->batch > 1 ? d->batch : 1;
-    p.ws_field = (p.ws_bytes + 255) & ~size_t(255);
+    p.ws_field = align256(p.ws_bytes);
+    p.wstride = int64_t(p.ws_field / es);
     p.chunk = batch_chunk(p.nbatch, p.ws_field);
     if (p.nbatch > 1) p.ws_bytes = p.ws_field * size_t(p.chunk);
-    p.ltl = log2_pow2(int64_t(p.tc) << p.log_k);
     p.row_log_g = p.fold && !p.r2c_t ? 0 : tuning().row_log_g;      // the row pairs of a fold are not siblings: no XCD grouping
     p.nt_in = nt_in_for(p.r2c ? size_t(M) * size_t(N) * es / 2 : size_t(p.nbatch) * size_t(rows) * size_t(d->in_x.len) * es);
     p.nt_out = col_store_nt(d, p.fold ? p.logm - 1 : -1);
@@ -207,14 +193,10 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
     }
     if (!(p.big_rn && p.big_rm && (p.big_rn > 1 || p.big_rm > 1)) || (d->flags & (PM_FLAG_PASS1_ONLY | PM_FLAG_PASS2_ONLY | PM_FLAG_SYNTH_INPUT)))
         p.big_rn = p.big_rm = 0;
-    p.mix_n = p.mix_m = false;
-    if (p.big_rn) {   // [Z: R_n planes of M x N/R_n | F (and the pre-processed rows before it): the same size]
-        p.tc = 0;
+    if (p.big_rn) {
+        p.lay.tc = 0;
         p.fold = false;
-        p.blue_n = p.blue_m = p.blue2d = p.blue_big = p.blue_fuse = false;
-        p.blue_off = 0;
-        const size_t arr = (size_t(M) * size_t(N) * es + 255) & ~size_t(255);
-        p.ws_bytes = 2 * arr;
+        p.ws_bytes = pair_ws(es, M, N).total;
         return p;
     }
     // the mixed-radix kernel addresses with 32-bit offsets: arrays of 4 GiB and more plan without it
@@ -223,22 +205,18 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
     p.mix_m = mixfit && p.logm < 0 && use_mix(M);
     p.blue_n = p.logn < 0 && use_blue(N, mixfit);
     p.blue_m = p.logm < 0 && use_blue(M, mixfit);
-    p.blue_off = (p.ws_bytes + 255) & ~size_t(255);
+    p.blue_off = align256(p.ws_bytes);
     const bool noflags = !(d->flags & (PM_FLAG_PASS1_ONLY | PM_FLAG_PASS2_ONLY | PM_FLAG_SYNTH_INPUT));
     p.blue2d = p.blue_n && p.blue_m && tuning().blue_2d && noflags;
     p.blue_big = !p.blue2d && tuning().blue_2d && noflags && blue_reach(N) && blue_reach(M) && (blue_needs_both(N, mixfit) || blue_needs_both(M, mixfit)) &&
                  (big_split(blue_conv_len(N)) > 1 || big_split(blue_conv_len(M)) > 1);
     p.blue_fuse = p.blue2d && !p.blue_big && tuning().blue_fuse;
-    if (p.blue_big) {   // [a (M x N) | c (M x N) | spectrum (MB1 x MB2) | workspace of the big transforms]
+    if (p.blue_big) {
         p.blue2d = true;
         p.blue_n = p.blue_m = false;
-        const size_t arr = (size_t(M) * size_t(N) * es + 255) & ~size_t(255);
-        const int64_t mb1 = blue_conv_len(M), mb2 = blue_conv_len(N);
-        const size_t spec = (size_t(mb1) * size_t(mb2) * es + 255) & ~size_t(255);
-        p.ws_bytes = 2 * arr + spec + 2 * spec;
-    } else if (p.blue2d) {
-        const size_t arr = (size_t(M) * size_t(N) * es + 255) & ~size_t(255);
-        p.ws_bytes = 2 * arr + blue2d_fused_ws(d->dtype, M, N);
+    }
+    if (p.blue2d) {
+        p.ws_bytes = blue2d_ws(d->dtype, M, N, p.blue_big).total;
     } else if (p.blue_n || p.blue_m) {
         const size_t a = p.blue_n ? blue_rows_scratch(es, rows, N) : 0, b = p.blue_m ? blue_cols_scratch(es, N, M) : 0;
         p.ws_bytes = p.blue_off + (a > b ? a : b);
@@ -250,9 +228,22 @@ Fft2Plan plan_fft2(const pm_fft2_desc* d, bool allow_r2c) {
 // and transposed stages (mix_cols_mul); the row passes are the engine's (a power-of-two row length) or the mixed-radix row kernel, on
 // NATURAL intermediates.  Three passes / 6 N^2 s bytes where two pm_fft2 calls move 8 N^2 s -- the reference takes any size through one
 // code path (prysm/propagation/angular_spectrum.py:9-42, prysm/convolution.py:9-31).  One field, complex output.
+// Pass A of the chain is the first pass of pm_fft2 on this shape: its descriptor and plan.  False when the transform planner would not
+// take the natural intermediate of pitch w_ld the chain's other passes read -- asked by the planner, so that the query never promises
+// a chain the run then refuses, and by the route.
+bool fused_mix_pass_a(const pm_fft2_desc* d, int64_t w_ld, pm_fft2_desc& da, Fft2Plan& pa) {
+    da = *d;
+    da.flags = (d->flags & PM_FLAG_REAL_INPUT) | PM_FLAG_PASS1_ONLY;
+    da.mul_kind = PM_MUL_NONE;
+    da.direction = -1;
+    da.batch = 0;
+    pa = plan_fft2(&da);
+    return !(pa.lay.tc != 0 || pa.w_ld != w_ld || pa.blue_n || pa.blue2d || pa.big_rn);
+}
+
 bool plan_fused_mix(const pm_fft2_desc* d, FusedPlan& p) {
     const int64_t M = d->in_y.n, N = d->in_x.n;
-    const size_t es = d->dtype == PM_C64 ? 8 : 16;
+    const size_t es = elem_size(d->dtype);
     if (!tuning().mix_fused || !use_mix(M) || !(p.logn >= 0 || use_mix(N)) || d->batch > 1) return false;
     if (d->flags & (PM_FLAG_SYNTH_INPUT | PM_FLAG_SYNTH_PACKED | PM_FLAG_PASS1_ONLY | PM_FLAG_PASS2_ONLY | PM_FLAG_NORM_DC)) return false;
     if (d->epilogue != PM_EPI_NONE || d->in_y.len <= 0) return false;
@@ -260,22 +251,14 @@ bool plan_fused_mix(const pm_fft2_desc* d, FusedPlan& p) {
     p.w_ld = (N + line - 1) / line * line;
     if (!mix_fits(N, d->in_ld, es, false) || !mix_fits(M, p.w_ld, es, true) || !mix_fits(N, d->out_ld, es, false) || !mix_fits(N, p.w_ld, es, false))
         return false;
-    {   // pass A is the first pass of pm_fft2 on this shape (fused_mix_run): its planner must take the same natural intermediate, or the
-        // query below would promise a chain the run then refuses
-        pm_fft2_desc da = *d;
-        da.flags = (d->flags & PM_FLAG_REAL_INPUT) | PM_FLAG_PASS1_ONLY;
-        da.mul_kind = PM_MUL_NONE;
-        da.direction = -1;
-        da.batch = 0;
-        const Fft2Plan pa = plan_fft2(&da);
-        if (pa.tc != 0 || pa.w_ld != p.w_ld || pa.blue_n || pa.blue2d || pa.big_rn) return false;
-    }
+    pm_fft2_desc da;
+    Fft2Plan pa;
+    if (!fused_mix_pass_a(d, p.w_ld, da, pa)) return false;
     p.mixmid = true;     // (plan_fused zeroed the fields this chain does not use)
     p.inplace = d->in_y.len == M;
-    p.w1_bytes = (size_t(d->in_y.len) * size_t(p.w_ld) * es + 255) & ~size_t(255);
-    p.w2_bytes = p.inplace ? 0 : ((size_t(M) * size_t(p.w_ld) * es + 255) & ~size_t(255));
+    p.cut = fused_ws(size_t(d->in_y.len) * size_t(p.w_ld) * es, size_t(M) * size_t(p.w_ld) * es, p.inplace);
     p.nbatch = p.chunk = 1;
-    p.ws_bytes = p.w1_bytes + p.w2_bytes;
+    p.ws_bytes = p.cut.field();
     p.nt_out = row_store_nt(size_t(d->out_y.len) * size_t(d->out_x.len) * es);
     return true;
 }
@@ -288,27 +271,25 @@ bool plan_fused(const pm_fft2_desc* d, FusedPlan& p) {
     p.w_ld = N;
     if (p.logm < 0) return plan_fused_mix(d, p);
     if (p.logn < 0) return false;
-    const size_t es = d->dtype == PM_C64 ? 8 : 16;
+    const size_t es = elem_size(d->dtype);
     // fold (see fold_legal): the input side only.  The output side is deliberately left out: the last row pass unfolds the row pairs and
     // rebuilds whole rows before the output window and its rotation apply, and the multiplier is the chain's own middle pass
     p.fold = fold_input_ok(d, p.logn, p.logm) && fold_auto(p.logm);
-    p.tc = col_tile_width_for(d->dtype, p.fold ? p.logm - 1 : p.logm, 0);
-    p.log_k = tuning().log_k >= 0 ? tuning().log_k : auto_log_k(N);
+    int log_k = tuning().log_k >= 0 ? tuning().log_k : auto_log_k(N);
     // folded 4096^2 complex64: 16 KiB row pieces measured 182.7 vs 188.7 us for the chain (see plan_fft2)
-    if (tuning().log_k < 0 && p.fold && d->dtype == PM_C64 && N == 4096 && M == 4096) p.log_k = 8;
-    while (p.log_k > 0 && (N % (int64_t(p.tc) << p.log_k)) != 0) --p.log_k;
-    const int64_t tl = int64_t(p.tc) << p.log_k, ntl = (N + tl - 1) / tl;
+    if (tuning().log_k < 0 && p.fold && d->dtype == PM_C64 && N == 4096 && M == 4096) log_k = 8;
+    // the layout of W2 (all M rows; folded: two planes of M/2); W1 is the same with the stored input rows, at least one
+    p.lay = TiledLayout::make(col_tile_width_for(d->dtype, p.fold ? p.logm - 1 : p.logm, 0), log_k, N, M, p.fold);
     p.inplace = d->in_y.len == M;
-    p.w1_bytes = size_t(ntl) * size_t(d->in_y.len > 0 ? d->in_y.len : 1) * size_t(tl) * es;
-    p.w2_bytes = p.inplace ? 0 : size_t(ntl) * size_t(M) * size_t(tl) * es;
-    p.w1_bytes = (p.w1_bytes + 255) & ~size_t(255);
-    p.w2_bytes = (p.w2_bytes + 255) & ~size_t(255);
+    TiledLayout w1 = p.lay;
+    if (!p.inplace) w1.rows = d->in_y.len > 0 ? d->in_y.len : 1;
+    p.cut = fused_ws(w1.bytes(es), p.lay.bytes(es), p.inplace);
+    p.wstride = int64_t(p.cut.field() / es);
     p.nbatch = d->batch > 1 ? d->batch : 1;
-    p.chunk = batch_chunk(p.nbatch, p.w1_bytes + p.w2_bytes);
-    p.ws_bytes = (p.w1_bytes + p.w2_bytes) * size_t(p.chunk);
-    p.ltl = log2_pow2(tl);
+    p.chunk = batch_chunk(p.nbatch, p.cut.field());
+    p.ws_bytes = p.cut.field() * size_t(p.chunk);
     p.row_log_g = p.fold ? 0 : tuning().row_log_g;      // (as in plan_fft2)
-    p.col_log_g = sibling_log_g(p.log_k);
+    p.col_log_g = sibling_log_g(p.lay.log_k);
     p.colmul_mode = tuning().colmul_mode;
     p.nt_in = nt_in_for(size_t(p.nbatch) * size_t(d->in_y.len) * size_t(d->in_x.len) * es);
     p.nt_out = row_store_nt(size_t(p.nbatch) * size_t(d->out_y.len) * size_t(d->out_x.len) * es);
@@ -390,14 +371,10 @@ int check_fft2(const pm_fft2_desc* d) {
 //   axis 0 (columns)  decimation in time: the sub-sequence r is rows r, r + R, ... of the caller's array -- a leading dimension of R
 //                     rows and the stored window cut to the rows of that residue -- R engine column passes -> big_finish combines;
 //                     workspace batch n
-size_t fft1_big_scratch(size_t es, int axis, int64_t batch, int64_t n) {
-    const size_t arr = (size_t(batch) * size_t(n) * es + 255) & ~size_t(255);
-    return axis == 1 ? 2 * arr : arr;
-}
-
 
 bool herm_conv_plan(const pm_fft2_desc* d, HermConvPlan& p) {
     const int64_t M = d->in_y.n, N = d->in_x.n;
+    p = HermConvPlan{};
     p.logn = engine_log2(N);
     p.logm = engine_log2(M);
     if (!(d->flags & PM_FLAG_REAL_INPUT) || (d->flags & (PM_FLAG_SYNTH_INPUT | PM_FLAG_PASS1_ONLY | PM_FLAG_PASS2_ONLY))) return false;
@@ -416,16 +393,14 @@ bool herm_conv_plan(const pm_fft2_desc* d, HermConvPlan& p) {
     p.fold = (f > 0 || (f < 0 && (p.logm >= 13 || (p.logm == 12 && d->dtype == PM_C128)))) && p.logm >= 2 &&
              (p.logn == 12 || (p.logn == 13 && d->dtype == PM_C64)) &&
              (d->in_y.shift == 0 || d->in_y.shift == M / 2);
-    p.tc = col_tile_width_for(d->dtype, p.fold ? p.logm - 1 : p.logm, 0);
     // layout tiles of 8 column tiles for complex64 (profiles/r06/exp_conv_fold.log: 4096^2 fp32 126.3 -> 122.3 us, 2048^2 55.5 -> 54.8; fp64 within noise: 4)
-    p.log_k = tuning().log_k >= 0 ? tuning().log_k : (d->dtype == PM_C64 ? 3 : 2);
-    while (p.log_k > 0 && ((N / 2) % (int64_t(p.tc) << p.log_k)) != 0) --p.log_k;
-    if ((N / 2) % p.tc) return false;
-    const size_t es = d->dtype == PM_C64 ? 8 : 16;
-    p.ws_bytes = size_t(M) * size_t(N / 2) * es;
-    p.ltl = log2_pow2(int64_t(p.tc) << p.log_k);
+    p.lay = TiledLayout::make(col_tile_width_for(d->dtype, p.fold ? p.logm - 1 : p.logm, 0), tuning().log_k >= 0 ? tuning().log_k : (d->dtype == PM_C64 ? 3 : 2),
+                              N / 2, M, p.fold);
+    if ((N / 2) % p.lay.tc) return false;     // whole column tiles only: the intermediate is then exactly M x N/2
+    const size_t es = elem_size(d->dtype);
+    p.ws_bytes = p.lay.bytes(es);
     p.row_log_g = p.fold ? 0 : tuning().row_log_g;
-    p.col_log_g = sibling_log_g(p.log_k);
+    p.col_log_g = sibling_log_g(p.lay.log_k);
     p.nt_out = row_store_nt(size_t(M) * size_t(N) * es / 2);
     return true;
 }
@@ -444,7 +419,7 @@ bool spectral_fast(const pm_fft2_desc* d, const Fft2Plan& p) {
            d->epilogue == PM_EPI_ABS2_ACCUM && d->batch <= 1 && d->mul_kind == PM_MUL_NONE && !p.r2c && !p.big_rn && !p.blue2d &&
            p.logn >= 5 && p.logn <= 12 /* its row kernel spills hundreds of registers at 8192-point rows (two rows per thread + the packed map) */ &&
            p.logm >= (p.fold ? 6 : 5) && p.logm - (p.fold ? 1 : 0) <= 11 /* the accumulating column kernel spills beyond 2048-point tiles */ &&
-           p.tc != 0 && p.col_var == 0 && d->in_y.len > 0 && p.logn + p.logm < tuning().spectral_area_log;
+           p.lay.tc != 0 && p.col_var == 0 && d->in_y.len > 0 && p.logn + p.logm < tuning().spectral_area_log;
 }
 
 int spectral_group(int32_t count) {
@@ -455,13 +430,13 @@ int spectral_group(int32_t count) {
 
 // One line that says which route a descriptor takes -- the planner's decisions (plan_fft2 / plan_fused / herm_conv_plan under the
 // calling thread's tuning knobs) in words.  Host logic only: callable without a GPU, so the routes of a table of shapes are pinned by
-// a CPU test (tests/test_host_logic.py) and a shape that falls to a slow route shows up there and not as a timing.
+// a CPU test (tests/test_capi_symbols.py) and a shape that falls to a slow route shows up there and not as a timing.
 // Does the row / column pass of this plan run on the composite register engine (fft_ce.h)?  The descriptor-level statement of what
 // ce_rows_view / ce_cols_view (fft_ce_kernels.h) accept, in ONE place (it was written out in pm_plan_explain, in fft2_run's
 // stack test and in the views): pm_plan_explain reports it, fft2_run sends (B, m, n) stacks out as grid.y by it.
 bool ce_rows_axis(const pm_fft2_desc* d, const Fft2Plan& p) {
     const bool f32 = d->dtype == PM_C64;
-    const size_t es = f32 ? 8 : 16;
+    const size_t es = elem_size(d->dtype);
     const int64_t N = d->in_x.n;
     return p.mix_n && tuning().mix_engine && !(d->flags & PM_FLAG_REAL_INPUT) && (f32 || !(d->flags & PM_FLAG_SYNTH_INPUT)) &&
            (f32 ? ce_has_plan<float>(int(N)) : ce_has_plan<double>(int(N))) && ce_fits32(kCeMaxSeqs * d->in_ld + 2 * N, es) &&
@@ -469,7 +444,7 @@ bool ce_rows_axis(const pm_fft2_desc* d, const Fft2Plan& p) {
 }
 bool ce_cols_axis(const pm_fft2_desc* d, const Fft2Plan& p) {
     const bool f32 = d->dtype == PM_C64;
-    const size_t es = f32 ? 8 : 16;
+    const size_t es = elem_size(d->dtype);
     const int64_t M = d->in_y.n, N = d->in_x.n;
     const bool whole_out = d->out_y.off == 0 && d->out_y.len == M && d->out_x.off == 0 && d->out_x.len == N;
     return p.mix_m && tuning().mix_engine && whole_out && d->mul_kind == PM_MUL_NONE && d->epilogue <= PM_EPI_ABS2_ACCUM &&
@@ -547,17 +522,17 @@ int pm_plan_explain(const pm_fft2_desc* d, int32_t op, char* buf, size_t n) {
                  M / 2, p.ws_bytes, p.col_log_g, p.fold ? " fold" : "");
     } else if (p.r2c) {
         snprintf(buf, n, "fft2 %lldx%lld %s: route=hermitian%s rows=stockham-r2c(%lld) cols=stockham(%lld%s) tile=%d log_k=%d ws=%zu g=%d", M, N, dt,
-                 p.fold ? "-fold" : "", N / 2, p.fold ? M / 2 : M, p.fold ? "x2" : "", p.tc, p.log_k, p.ws_bytes, p.col_log_g);
+                 p.fold ? "-fold" : "", N / 2, p.fold ? M / 2 : M, p.fold ? "x2" : "", p.lay.tc, p.lay.log_k, p.ws_bytes, p.col_log_g);
     } else {
         const bool en = p.logn >= 0, em = p.logm >= 0;
         // a composite axis whose length has a compile-time plan runs on the register engine (fft_ce.h) when the view is plain
         const bool ce_n = ce_rows_axis(d, p), ce_m = ce_cols_axis(d, p);
         char g[16] = "";
-        if (p.tc) snprintf(g, sizeof g, " g=%d", p.col_log_g);     // the engine's tiled column pass
+        if (p.lay.tc) snprintf(g, sizeof g, " g=%d", p.col_log_g);     // the engine's tiled column pass
         snprintf(buf, n, "fft2 %lldx%lld %s: route=%s rows=%s(%lld) cols=%s(%lld%s) tile=%d log_k=%d chunk=%lld ws=%zu%s", M, N, dt,
                  (en && em) ? (p.fold ? "engine-fold" : "engine") : ((p.mix_n || !p.blue_n) && (p.mix_m || !p.blue_m) && (p.mix_n || p.mix_m) ? "natural-mixed" : "natural"),
                  ce_n ? "mixed-radix-registers" : axis_route(en, p.mix_n, p.blue_n), N, ce_m ? "mixed-radix-registers" : axis_route(em, p.mix_m, p.blue_m),
-                 p.fold ? M / 2 : M, p.fold ? "x2" : "", p.tc, p.log_k, (long long)p.chunk, p.ws_bytes, g);
+                 p.fold ? M / 2 : M, p.fold ? "x2" : "", p.lay.tc, p.lay.log_k, (long long)p.chunk, p.ws_bytes, g);
     }
     return 0;
 }
@@ -565,8 +540,7 @@ int pm_plan_explain(const pm_fft2_desc* d, int32_t op, char* buf, size_t n) {
 size_t pm_fft2_spectral_workspace(const pm_fft2_desc* d, int32_t count) {
     if (check_fft2(d) || count <= 0) return 0;
     const Fft2Plan p = plan_fft2(d);
-    size_t need = spectral_fast(d, p) ? p.ws_field * size_t(spectral_group(count)) : p.ws_bytes;
-    return need;
+    return spectral_fast(d, p) ? p.ws_field * size_t(spectral_group(count)) : p.ws_bytes;
 }
 
 size_t pm_fft2_mul_ifft2_workspace(const pm_fft2_desc* d) {
@@ -576,14 +550,13 @@ size_t pm_fft2_mul_ifft2_workspace(const pm_fft2_desc* d) {
         return herm_conv_plan(d, hp) ? hp.ws_bytes : 0;
     }
     FusedPlan p;
-    if (!plan_fused(d, p)) return 0;
-    return p.ws_bytes;
+    return plan_fused(d, p) ? p.ws_bytes : 0;
 }
 
 size_t pm_fft1_workspace(int32_t dtype, int32_t axis, int64_t batch, int64_t n) {
     if ((dtype != PM_C64 && dtype != PM_C128) || batch <= 0) return 0;
-    const size_t es = dtype == PM_C64 ? 8 : 16;
-    if (big_split(n) > 1) return fft1_big_scratch(es, axis, batch, n);     // 16384 / 32768 and 3 / 5 / 7 x 2^k: a radix-R step
+    const size_t es = elem_size(dtype);
+    if (big_split(n) > 1) return pair_ws(es, batch, n, axis == 1).total;     // 16384 / 32768 and 3 / 5 / 7 x 2^k: a radix-R step
     if (!use_blue(n)) return 0;
     return axis == 1 ? blue_rows_scratch(es, batch, n) : blue_cols_scratch(es, batch, n);
 }

@@ -213,12 +213,15 @@ def _desc(m, n, dt='c64', Q=None, real=False, mul=False, epi=0, batch=0, synth=F
     return d
 
 
-def _route(lib, m, n, dt='c64', op=0, **kw):
+def _explain(lib, d, op=0):
     from prysm_amd import _lib as L
-    d = _desc(m, n, dt, **kw)
     buf = ctypes.create_string_buffer(256)
     L.check(lib.pm_plan_explain(ctypes.byref(d), op, buf, 256))
     return buf.value.decode()
+
+
+def _route(lib, m, n, dt='c64', op=0, **kw):
+    return _explain(lib, _desc(m, n, dt, **kw), op)
 
 
 # (arguments of _route, substrings the line must contain): the routes of round 5.  A change of the planner that moves a shape shows up
@@ -399,6 +402,58 @@ def test_explain_shows_the_launch_choices_the_plan_makes(lib):
         assert _route(lib, 4096, 4096).endswith(' g=2') and _route(lib, 8192, 8192, **mtf).endswith(' g=2')
     with L.tuning_local(col_log_g=7):     # the sibling group of the tiled column pass stops at 2^5
         assert _route(lib, 4096, 4096).endswith(' g=5')
+
+
+def test_workspace_bytes_of_the_routes_the_tables_above_do_not_pin(lib):
+    """Each route's own query, to the byte (recorded from the build before the layout moved into csrc/ws_layout.h): planner and runner
+    read ONE description of every intermediate, and a change of it shows up here before a kernel writes past a workspace."""
+    from prysm_amd import _lib as L
+    MiB = 1 << 20
+
+    def ws(d):
+        return lib.pm_fft2_workspace(ctypes.byref(d))
+
+    def chain_ws(d):
+        return lib.pm_fft2_mul_ifft2_workspace(ctypes.byref(d))
+
+    def real_chain(m, n, dt='c64'):
+        d = _desc(m, n, dt, real=True)
+        d.flags |= L.PM_FLAG_REAL_OUTPUT
+        d.mul_kind, d.mul = L.PM_MUL_FULL, 16
+        return d
+    # pm_fft2_workspace.  Folded hermitian-fold, 8192^2 fp32: the route's half spectrum is 8192 x 4096 x 8 (two planes of 4096 rows); the
+    # query also covers the complex path that takes over from an unaligned real array, 8192 x 8192 x 8
+    mtf = _desc(8192, 8192, real=True, epi=L.PM_EPI_ABS)
+    assert 'route=hermitian-fold' in _route(lib, 8192, 8192, real=True, epi=L.PM_EPI_ABS) and 'ws=268435456 ' in _route(lib, 8192, 8192, real=True, epi=L.PM_EPI_ABS)
+    assert ws(mtf) == 536870912
+    # a batch whose last chunk is partial: 100 stored rows of 256 -> 100 x 256 x 8 = 204800 B per field, 655 fields per 128 MiB chunk, 1000 = 655 + 345
+    d = _desc(256, 256, batch=1000)
+    d.in_y = L.pm_axis(256, 100, 78, 128)
+    assert ws(d) == 134144000 and 'chunk=655 ' in _explain(lib, d)
+    assert ws(_desc(1024, 1024, batch=100)) == 128 * MiB         # 16 fields of 8 MiB; 100 = 6 x 16 + 4
+    # pm_fft2_mul_ifft2_workspace.  hermitian-chain: the half spectrum M x N/2, in place
+    assert chain_ws(real_chain(2048, 2048)) == 16777216 and 'route=hermitian-chain' in _explain(lib, real_chain(2048, 2048), 1)      # 2048 x 1024 x 8
+    assert chain_ws(real_chain(4096, 4096, 'c128')) == 134217728         # folded (4096 rows of complex128): two planes of 2048 x 2048 x 16
+    assert chain_ws(real_chain(8192, 8192)) == 268435456                 # folded: two planes of 4096 x 4096 x 8
+    # the fused chain with fewer stored rows than M: separate W1 (512 x 1024 x 8) | W2 (1024 x 1024 x 8)
+    assert chain_ws(_desc(1024, 1024, Q=2, mul=True)) == 4194304 + 8388608
+    d = _desc(256, 256, mul=True)
+    d.in_y = L.pm_axis(256, 3, 0, 0)
+    assert chain_ws(d) == 6144 + 524288                                  # 3 x 256 x 8 | 256 x 256 x 8
+    # a fused stack: in place 8 MiB per field, 16 fields per chunk; padded 12 MiB per field ([W1 | W2] above), 10 per chunk
+    assert chain_ws(_desc(1024, 1024, mul=True, batch=40)) == 16 * 8 * MiB
+    assert chain_ws(_desc(1024, 1024, Q=2, mul=True, batch=40)) == 10 * 12 * MiB
+    # pm_fft2_spectral_workspace: one 8 MiB intermediate per wavelength of a group
+    d = _desc(1024, 1024, synth=True, epi=L.PM_EPI_ABS2_ACCUM)
+    d.flags |= L.PM_FLAG_SYNTH_PACKED
+    assert lib.pm_fft2_spectral_workspace(ctypes.byref(d), 3) == 3 * 8 * MiB and lib.pm_fft2_spectral_workspace(ctypes.byref(d), 8) == 8 * 8 * MiB
+    assert lib.pm_fft2_spectral_workspace(ctypes.byref(d), 20) == 8 * 8 * MiB        # groups of at most 8
+    d = _desc(32, 32, synth=True, epi=L.PM_EPI_ABS2_ACCUM)
+    d.flags |= L.PM_FLAG_SYNTH_PACKED
+    assert lib.pm_fft2_spectral_workspace(ctypes.byref(d), 3) == 3 * 8192
+    # pm_fft1_workspace, 16384 = 2 x 8192: rows [Y | Z], columns one array
+    assert lib.pm_fft1_workspace(L.PM_C64, 1, 4, 16384) == 2 * 4 * 16384 * 8 and lib.pm_fft1_workspace(L.PM_C64, 0, 4, 16384) == 4 * 16384 * 8
+    assert lib.pm_fft1_workspace(L.PM_C128, 1, 3, 16384) == 2 * 3 * 16384 * 16 and lib.pm_fft1_workspace(L.PM_C128, 0, 3, 16384) == 3 * 16384 * 16
 
 
 # PM_TUNE of the second child of the test below: one live knob

@@ -481,3 +481,154 @@ def test_tuning_local_blocks_nest(pa):
                 pass
         assert 'mixed-radix' not in route(1000) and 'engine-fold' in route(4096)
     assert 'mixed-radix' in route(1000)
+
+
+# ----------------------------------------------------------------------------- no route writes outside the workspace its query asked for
+
+_GUARD_BYTE = 0xA5
+
+
+class _Guarded:
+    """A workspace of exactly `nbytes` (what the route's query asked for) with a guard behind it, at least as long and at least 64 KiB,
+    filled with one byte.  prysm_amd._lib.workspace hands out a buffer that only grows, so an overrun of a few rows lands in it unseen."""
+
+    def __init__(self, nbytes):
+        assert nbytes > 0
+        self.nbytes = int(nbytes)
+        self.buf = torch.full((self.nbytes + max(self.nbytes, 65536),), _GUARD_BYTE, dtype=torch.uint8, device='cuda')
+
+    def ptr(self):
+        return ctypes.c_void_p(self.buf.data_ptr())
+
+    def intact(self):
+        torch.cuda.synchronize()
+        return bool((self.buf[self.nbytes:] == _GUARD_BYTE).all())
+
+
+def _explain_desc(lib, d, op):
+    from prysm_amd import _lib as L
+    buf = ctypes.create_string_buffer(256)
+    L.check(lib.pm_plan_explain(ctypes.byref(d), op, buf, 256))
+    return buf.value.decode()
+
+
+def _guard_fft2(x, route, shape=None, in_off=(0, 0), epilogue=0):
+    """pm_fft2 on a guarded workspace == _ops.fft2; the planner's line must hold `route` (several pieces: a|b)"""
+    from prysm_amd import _lib as L, _ops
+    lib = L.load()
+    d = L.pm_fft2_desc()
+    x, _, (om, on) = _ops._fill_views(d, x, shape, in_off, (0, 0), None, (0, 0), (0, 0))
+    d.direction, d.epilogue, d.scale, d.weight = -1, epilogue, 1.0, 1.0
+    cdt = L.cdtype_of(x)
+    out = torch.zeros(tuple(x.shape[:-2]) + (om, on), dtype=cdt if epilogue == L.PM_EPI_NONE else L._REAL_OF[cdt], device='cuda')
+    d.out_ld, d.out_bstride = on, (om * on if x.dim() == 3 else 0)
+    line = _explain_desc(lib, d, 0)
+    assert all(w in line for w in route.split('|')), line
+    ws = _Guarded(lib.pm_fft2_workspace(ctypes.byref(d)))
+    L.check(lib.pm_fft2(ctypes.byref(d), L.ptr(x), L.ptr(out), ws.ptr(), ws.nbytes, L.stream_ptr()))
+    assert ws.intact(), line
+    assert torch.equal(out, _ops.fft2(x, direction=-1, scale=1.0, shape=shape, in_off=in_off, epilogue=epilogue)), line
+
+
+def _guard_chain(x, mul, route, shape=None, in_off=(0, 0), real_out=False):
+    """pm_fft2_mul_ifft2 on a guarded workspace == _ops.fft2_mul_ifft2"""
+    from prysm_amd import _lib as L, _ops
+    lib = L.load()
+    d = L.pm_fft2_desc()
+    x, _, (om, on) = _ops._fill_views(d, x, shape, in_off, (0, 0), None, (0, 0), (0, 0))
+    d.direction, d.scale, d.weight = -1, 1.0, 1.0
+    _ops._fill_mul(d, x, mul, None, False, [])
+    if real_out:
+        d.flags |= L.PM_FLAG_REAL_OUTPUT
+    out = torch.zeros((om, on), dtype=L._REAL_OF[L.cdtype_of(x)] if real_out else L.cdtype_of(x), device='cuda')
+    d.out_ld = on
+    line = _explain_desc(lib, d, 1)
+    assert route in line, line
+    ws = _Guarded(lib.pm_fft2_mul_ifft2_workspace(ctypes.byref(d)))
+    L.check(lib.pm_fft2_mul_ifft2(ctypes.byref(d), L.ptr(x), L.ptr(out), ws.ptr(), ws.nbytes, L.stream_ptr()))
+    assert ws.intact(), line
+    assert torch.equal(out, _ops.fft2_mul_ifft2(x, scale=1.0, mul=mul, shape=shape, in_off=in_off, real_out=real_out)), line
+
+
+def _guard_fft1(x, axis):
+    """pm_fft1_ws on a guarded workspace == _ops.fft1"""
+    from prysm_amd import _lib as L, _ops
+    lib = L.load()
+    rows, cols = x.shape
+    n, batch = (rows, cols) if axis == 0 else (cols, rows)
+    t = _ops._axis(n)
+    out = torch.zeros_like(x)
+    ws = _Guarded(lib.pm_fft1_workspace(L.code(x), axis, batch, n))
+    L.check(lib.pm_fft1_ws(L.code(x), -1, axis, batch, ctypes.byref(t), ctypes.byref(t), 1.0, L.ptr(x), x.stride(0), L.ptr(out), out.stride(0),
+                           ws.ptr(), ws.nbytes, L.stream_ptr()))
+    assert ws.intact(), (n, axis)
+    assert torch.equal(out, _ops.fft1(x, axis=axis)), (n, axis)
+
+
+def test_no_route_writes_outside_the_workspace_its_query_asked_for(pa):
+    """One case per route at the smallest shape the route takes (the route asserted from pm_plan_explain, so that a case cannot drift to
+    another one): the C ABI called directly with a workspace of exactly the queried size and a guard of at least that length and 64 KiB
+    behind it.  The guard is untouched and the result is the one of the same call through prysm_amd._ops.  bluestein-2d-big is left
+    out (its smallest workspace is several GiB; its own test and the pinned size cover it)."""
+    from prysm_amd import _lib as L, _ops
+    lib = L.load()
+    g = torch.Generator(device='cuda').manual_seed(47)
+
+    def c(*shape, dt=torch.complex64):
+        return torch.randn(*shape, dtype=dt, device='cuda', generator=g)
+
+    def r(*shape, dt=torch.float32):
+        return torch.randn(*shape, dtype=dt, device='cuda', generator=g)
+    # the engine: whole, padded, folded in both precisions, a stack
+    _guard_fft2(c(16, 32), 'route=engine ')
+    _guard_fft2(c(8, 16), 'route=engine ', shape=(16, 32), in_off=(4, 8))
+    with L.tuning_local(fold=1):
+        _guard_fft2(c(8, 2048), 'route=engine-fold')
+        _guard_fft2(c(8, 2048, dt=torch.complex128), 'route=engine-fold')
+    _guard_fft2(c(3, 32, 32), 'route=engine ')
+    # the Hermitian forms of a real field
+    with L.tuning_local(herm_t=0, r2c=2):
+        _guard_fft2(r(32, 64), 'route=hermitian ', epilogue=L.PM_EPI_ABS)
+        with L.tuning_local(fold=1):
+            _guard_fft2(r(32, 64), 'route=hermitian-fold', epilogue=L.PM_EPI_ABS)
+    _guard_fft2(r(32, 32), 'route=hermitian-transposed', epilogue=L.PM_EPI_ABS)
+    with L.tuning_local(herm_t_fold=1):
+        _guard_fft2(r(2048, 32), 'route=hermitian-transposed| fold', epilogue=L.PM_EPI_ABS)
+    # the chains
+    _guard_chain(c(16, 32), c(16, 32), 'route=fused ')
+    _guard_chain(c(8, 16), c(16, 32), 'route=fused ', shape=(16, 32), in_off=(4, 8))
+    with L.tuning_local(fold=1):
+        _guard_chain(c(8, 2048), c(8, 2048), 'mid=stockham-pair fold')
+    with L.tuning_local(r2c=2):
+        _guard_chain(r(2, 64), c(2, 64), 'route=hermitian-chain', real_out=True)
+        with L.tuning_local(fold=1):
+            _guard_chain(r(4, 4096), c(4, 4096), 'route=hermitian-chain', real_out=True)
+    _guard_chain(c(96, 100), c(96, 100), 'route=fused-composite')
+    # composite, Bluestein and radix-step lengths (the smallest shapes the planner answers these routes for)
+    _guard_fft2(c(36, 36), 'route=natural-mixed')
+    _guard_fft2(c(2, 97), 'rows=bluestein')
+    _guard_fft2(c(97, 97), 'route=bluestein-2d ')
+    _guard_fft2(c(2, 16384), 'route=radix-step')
+    _guard_fft2(c(16384, 2), 'route=radix-step')
+    # 1-D: the radix-R step on both axes, a prime length on Bluestein's
+    _guard_fft1(c(2, 16384), 1)
+    _guard_fft1(c(16384, 2), 0)
+    _guard_fft1(c(2, 97), 1)
+    _guard_fft1(c(97, 2), 0)
+    # the grouped wavelength loop: three intermediates
+    packed = _ops.pack_amp_opd((r(32, 32) > 0).float(), r(32, 32))
+    ks, wts = [0.011, 0.012, 0.013], [1.0, 0.5, 0.25]
+    d = L.pm_fft2_desc()
+    _ops._fill_views(d, packed, None, (0, 0), (0, 0), None, (0, 0), (0, 0))
+    d.direction, d.epilogue, d.scale, d.weight, d.out_ld = -1, L.PM_EPI_ABS2_ACCUM, 1.0, 1.0, 32
+    d.flags |= L.PM_FLAG_SYNTH_INPUT | L.PM_FLAG_SYNTH_PACKED
+    nbytes = lib.pm_fft2_spectral_workspace(ctypes.byref(d), 3)
+    assert nbytes == 3 * 32 * 32 * 8 and 'route=engine ' in _explain_desc(lib, d, 0)      # the grouped form: one intermediate per wavelength
+    ws, acc = _Guarded(nbytes), torch.zeros(32, 32, dtype=torch.float32, device='cuda')
+    L.check(lib.pm_fft2_spectral(ctypes.byref(d), 3, (ctypes.c_double * 3)(*ks), (ctypes.c_double * 3)(*wts), L.ptr(packed), L.ptr(acc), ws.ptr(),
+                                 ws.nbytes, L.stream_ptr()))
+    assert ws.intact()
+    ref = _ops.fft2(packed, direction=-1, scale=1.0, epilogue=L.PM_EPI_ABS2_ACCUM, synth=('packed', ks[0]), spectral=(ks, wts),
+                    out=torch.zeros(32, 32, dtype=torch.float32, device='cuda'))
+    assert torch.equal(acc, ref) and float(acc.abs().max()) > 0
+

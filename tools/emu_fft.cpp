@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "fft_io.h"
+#include "ws_layout.h"
 #include "bluestein.h"
 
 using namespace pm;
@@ -163,17 +164,15 @@ static void test_2d(int in_rows, int in_cols, bool shifts, int epilogue, bool in
     using RC = FftCfg<T, LOGN, 1, 1, RBO, RCOMP>;      // row transform of length N (columns)
     using CC = FftCfg<T, LOGM, CCI, CE, CBO, CCOMP>;   // column transform of length M (rows)
     const int M = CC::N, N = RC::N, TC = CCI * CE;
-    const int TL = TC << log_k;
-    int log_tc = 0;
-    while ((1 << log_tc) < TL) ++log_tc;
+    const TiledLayout lay = TiledLayout::make(TC, log_k, N, in_rows);      // the planner's statement of W (csrc/ws_layout.h)
+    const int TL = int(lay.tl()), log_tc = lay.ltl, ntiles = lay.ntiles();
     std::mt19937 rng(LOGM * 17 + LOGN);
     std::normal_distribution<double> nd;
     std::vector<cx<T>> x(size_t(in_rows) * in_cols);
     for (auto& e : x) e = {T(nd(rng)), T(nd(rng))};
     const int offy = (M - in_rows + 1) / 2, offx = (N - in_cols + 1) / 2;  // pad2d: ceil(d/2)
     const int shy = shifts ? M / 2 : 0, shx = shifts ? N / 2 : 0;
-    const int ntiles = (N + TC - 1) / TC;
-    std::vector<cx<T>> W(size_t((N + TL - 1) / TL) * in_rows * TL, cx<T>{T(1e30), T(1e30)});
+    std::vector<cx<T>> W(size_t(lay.elems()), cx<T>{T(1e30), T(1e30)});
     auto twN = make_tw<T>(N);
     auto twM = make_tw<T>(M);
     // pass 1: one FFT per stored input row
@@ -184,7 +183,7 @@ static void test_2d(int in_rows, int in_cols, bool shifts, int epilogue, bool in
     const int coffy = (M - out_rows + 1) / 2, coffx = (N - out_cols + 1) / 2;  // crop_center: ceil(p/2)
     std::vector<cx<T>> out(size_t(out_rows) * out_cols, cx<T>{T(-3), T(-3)});
     std::vector<T> outr(size_t(out_rows) * out_cols, T(-3));
-    ColLoadTiled<T> cl{W.data(), in_rows, AxisMap{M, in_rows, offy, shy}, ntiles, log_k};
+    ColLoadTiled<T> cl{W.data(), in_rows, AxisMap{M, in_rows, offy, shy}, ntiles, lay.log_k};
     ColStoreNat<T> cs{};
     cs.dst = epilogue ? (void*)outr.data() : (void*)out.data();
     cs.ld = out_cols;
@@ -227,18 +226,17 @@ template <typename T, int LOGM, int LOGN, int RBO, int RCOMP, int CCI, int CE, i
 static void test_2d_fold(int in_cols, bool shifts, int epilogue, bool inverse, int out_rows, int out_cols, int log_k = 0) {
     using RC = FftCfg<T, LOGN, 1, 2, RBO, RCOMP>;
     using CC = FftCfg<T, LOGM - 1, CCI, CE, CBO, CCOMP>;
-    const int M = 1 << LOGM, H = M / 2, N = RC::N, TC = CCI * CE, TL = TC << log_k;
-    int log_tc = 0;
-    while ((1 << log_tc) < TL) ++log_tc;
+    const int M = 1 << LOGM, H = M / 2, N = RC::N, TC = CCI * CE;
+    const TiledLayout lay = TiledLayout::make(TC, log_k, N, M, true);
+    const int TL = int(lay.tl()), log_tc = lay.ltl, ntiles = lay.ntiles();
     std::mt19937 rng(LOGM * 19 + LOGN);
     std::normal_distribution<double> nd;
     std::vector<cx<T>> x(size_t(M) * in_cols);
     for (auto& e : x) e = {T(nd(rng)), T(nd(rng))};
     const int offx = (N - in_cols + 1) / 2;
     const int shy = shifts ? M / 2 : 0, shx = shifts ? N / 2 : 0;
-    const int ntiles = (N + TC - 1) / TC, ntl = (N + TL - 1) / TL;
-    const int64_t plane = int64_t(ntl) * H * TL;
-    std::vector<cx<T>> W(size_t(2 * plane), cx<T>{T(1e30), T(1e30)});
+    const int64_t plane = lay.plane();
+    std::vector<cx<T>> W(size_t(lay.elems()), cx<T>{T(1e30), T(1e30)});
     auto twN = make_tw<T>(N);
     auto twM = make_tw<T>(M);
     auto twH = make_tw<T>(H);
@@ -248,7 +246,7 @@ static void test_2d_fold(int in_cols, bool shifts, int epilogue, bool inverse, i
     const int coffy = (M - out_rows + 1) / 2, coffx = (N - out_cols + 1) / 2;
     std::vector<cx<T>> out(size_t(out_rows) * out_cols, cx<T>{T(-3), T(-3)});
     std::vector<T> outr(size_t(out_rows) * out_cols, T(-3));
-    ColLoadTiled<T> cl{W.data(), H, AxisMap{H, H, 0, 0}, ntiles, log_k, plane};
+    ColLoadTiled<T> cl{W.data(), H, AxisMap{H, H, 0, 0}, ntiles, lay.log_k, plane};
     ColStoreNat<T> cs{};
     cs.dst = epilogue ? (void*)outr.data() : (void*)out.data();
     cs.ld = 2 * out_cols;
@@ -331,10 +329,11 @@ template <typename T, int LOGM, int LOGN, int RBO, int CCI, int CE, int CBO, int
 static void test_fused(int in_rows, int in_cols, int out_rows, int out_cols, int log_k, bool separable, bool mconj, bool shifts) {
     using RC = FftCfg<T, LOGN, 1, 1, RBO, 1>;
     using CC = FftCfg<T, LOGM, CCI, CE, CBO, CCOMP>;
-    const int M = CC::N, N = RC::N, TC = CCI * CE, TL = TC << log_k;
-    int ltl = 0;
-    while ((1 << ltl) < TL) ++ltl;
+    const int M = CC::N, N = RC::N, TC = CCI * CE;
     std::mt19937 rng(LOGM * 19 + LOGN + log_k);
+    const TiledLayout lay = TiledLayout::make(TC, log_k, N, M);      // W2; W1 is the same with the stored rows
+    const TiledLayout lay1 = TiledLayout::make(TC, log_k, N, in_rows);
+    const int TL = int(lay.tl()), ltl = lay.ltl, ntiles = lay.ntiles();
     std::normal_distribution<double> nd;
     std::vector<cx<T>> x(size_t(in_rows) * in_cols), H(size_t(M) * N), hy(M), hx(N);
     for (auto& e : x) e = {T(nd(rng)), T(nd(rng))};
@@ -344,17 +343,16 @@ static void test_fused(int in_rows, int in_cols, int out_rows, int out_cols, int
     const int offy = (M - in_rows + 1) / 2, offx = (N - in_cols + 1) / 2;
     const int shy = shifts ? M / 2 : 0, shx = shifts ? N / 2 : 0;
     const int coffy = (M - out_rows + 1) / 2, coffx = (N - out_cols + 1) / 2;
-    const int ntl = (N + TL - 1) / TL, ntiles = (N + TC - 1) / TC;
-    std::vector<cx<T>> W1(size_t(ntl) * in_rows * TL, cx<T>{T(1e30), T(1e30)}), W2(size_t(ntl) * M * TL, cx<T>{T(1e30), T(1e30)});
+    std::vector<cx<T>> W1(size_t(lay1.elems()), cx<T>{T(1e30), T(1e30)}), W2(size_t(lay.elems()), cx<T>{T(1e30), T(1e30)});
     auto twN = make_tw<T>(N);
     auto twM = make_tw<T>(M);
     RowLoadNat<T> lp{x.data(), in_cols, AxisMap{N, in_cols, offx, shx}, in_rows, 0, 0};
     RowStoreTiled<T> sp{W1.data(), in_rows, ltl};
     emu_kernel<RC, false>((in_rows + RC::BO - 1) / RC::BO, lp, sp, twN.data());
     // pass B
-    ColLoadTiled<T> cl{W1.data(), in_rows, AxisMap{M, in_rows, offy, shy}, ntiles, log_k};
+    ColLoadTiled<T> cl{W1.data(), in_rows, AxisMap{M, in_rows, offy, shy}, ntiles, lay.log_k};
     MidMul<T> mm{separable ? MUL_SEPARABLE : MUL_FULL, mconj ? 1 : 0, separable ? hy.data() : H.data(), hx.data(), N, N};
-    ColStoreTiled<T> cst{W2.data(), M, ntiles, log_k};
+    ColStoreTiled<T> cst{W2.data(), M, ntiles, lay.log_k};
     {
         std::vector<Regs<CC>> regs(CC::NT);
         std::vector<typename LdsType<CC>::type> lds(CC::LDS_ELEMS + 1);
@@ -406,10 +404,10 @@ template <typename T, int LOGM, int LOGN, int RBO, int RCOMP, int CCI, int CE, i
 static void test_fused_fold(int in_cols, int out_rows, int out_cols, int log_k, bool separable, bool mconj, bool shifts) {
     using RC = FftCfg<T, LOGN, 1, 2, RBO, RCOMP>;
     using CC = FftCfg<T, LOGM - 1, CCI, CE, CBO, CCOMP>;
-    const int M = 1 << LOGM, Hh = M / 2, N = RC::N, TC = CCI * CE, TL = TC << log_k;
-    int ltl = 0;
-    while ((1 << ltl) < TL) ++ltl;
+    const int M = 1 << LOGM, Hh = M / 2, N = RC::N, TC = CCI * CE;
     std::mt19937 rng(LOGM * 23 + LOGN + log_k);
+    const TiledLayout lay = TiledLayout::make(TC, log_k, N, M, true);
+    const int TL = int(lay.tl()), ltl = lay.ltl, ntiles = lay.ntiles();
     std::normal_distribution<double> nd;
     std::vector<cx<T>> x(size_t(M) * in_cols), H(size_t(M) * N), hy(M), hx(N);
     for (auto& e : x) e = {T(nd(rng)), T(nd(rng))};
@@ -419,19 +417,18 @@ static void test_fused_fold(int in_cols, int out_rows, int out_cols, int log_k, 
     const int offx = (N - in_cols + 1) / 2;
     const int shy = shifts ? M / 2 : 0, shx = shifts ? N / 2 : 0;
     const int coffy = (M - out_rows + 1) / 2, coffx = (N - out_cols + 1) / 2;
-    const int ntl = (N + TL - 1) / TL, ntiles = (N + TC - 1) / TC;
-    const int64_t plane = int64_t(ntl) * Hh * TL;
-    std::vector<cx<T>> W(size_t(2 * plane), cx<T>{T(1e30), T(1e30)});
+    const int64_t plane = lay.plane();
+    std::vector<cx<T>> W(size_t(lay.elems()), cx<T>{T(1e30), T(1e30)});
     auto twN = make_tw<T>(N);
     auto twM = make_tw<T>(M);
     auto twH = make_tw<T>(Hh);
     RowLoadNat<T> lp{x.data(), in_cols, AxisMap{N, in_cols, offx, shx}, M, 0, 0, 0, 0, Hh};
     RowStoreFold<T> sp{W.data(), plane, Hh, ltl, twM.data(), shifts ? 1 : 0, 0};
     emu_kernel<RC, false>((Hh + RC::BO - 1) / RC::BO, lp, sp, twN.data());
-    ColLoadTiled<T> cl0{W.data(), Hh, AxisMap{Hh, Hh, 0, 0}, ntiles, log_k, plane};
+    ColLoadTiled<T> cl0{W.data(), Hh, AxisMap{Hh, Hh, 0, 0}, ntiles, lay.log_k, plane};
     MidMul<T> mm0{separable ? MUL_SEPARABLE : MUL_FULL, mconj ? 1 : 0, separable ? hy.data() : H.data(), hx.data(), 2 * N, N,
                   separable ? 1 : N, 0, 2};
-    ColStoreTiled<T> cst0{W.data(), Hh, ntiles, log_k, plane};
+    ColStoreTiled<T> cst0{W.data(), Hh, ntiles, lay.log_k, plane};
     for (int b = 0; b < 2; ++b) {
         const auto cl = at_batch(cl0, b);
         const auto mm = at_batch(mm0, b);
@@ -644,10 +641,10 @@ static void test_blue2d_fused(int n1, int n2, int in_rows, int in_cols, int offy
                               int out_rows, int out_cols, int ooffy, int ooffx, int oshy, int oshx, int epilogue, int log_k) {
     using RC = FftCfg<T, LOGN, 1, RE, RBO, 1>;
     using CC = FftCfg<T, LOGM, CCI, CE, CBO, CCOMP>;
-    const int M = CC::N, N = RC::N, TC = CCI * CE, TL = TC << log_k;
+    const int M = CC::N, N = RC::N, TC = CCI * CE;
     if (M != blue_conv_len(n1) || N != blue_conv_len(n2)) { printf("blue2d fused: convolution length mismatch\n"); ++g_fail; return; }
-    int ltl = 0;
-    while ((1 << ltl) < TL) ++ltl;
+    const TiledLayout lay = TiledLayout::make(TC, log_k, N, n1);      // W1, and the rows of W2 the cropping store keeps
+    const int ltl = lay.ltl, ntiles = lay.ntiles();
     std::mt19937 rng(n1 * 31 + n2);
     std::normal_distribution<double> nd;
     std::vector<cx<T>> x(size_t(in_rows) * in_cols);
@@ -657,8 +654,7 @@ static void test_blue2d_fused(int n1, int n2, int in_rows, int in_cols, int offy
     std::vector<cx<T>> t1, t2;
     blue_make_tables<T>(n1, M, t1);
     blue_make_tables<T>(n2, N, t2);
-    const int ntl = (N + TL - 1) / TL, ntiles = (N + TC - 1) / TC;
-    std::vector<cx<T>> W1(size_t(ntl) * n1 * TL, cx<T>{T(1e30), T(1e30)}), W2(size_t(ntl) * n1 * TL, cx<T>{T(1e30), T(1e30)});
+    std::vector<cx<T>> W1(size_t(lay.elems()), cx<T>{T(1e30), T(1e30)}), W2(size_t(lay.elems()), cx<T>{T(1e30), T(1e30)});
     auto twN = make_tw<T>(N);
     auto twM = make_tw<T>(M);
     Blue2dIn<T> view{real_in ? (const void*)xr.data() : (const void*)x.data(), in_cols, AxisMap{n1, in_rows, offy, shy},
@@ -666,9 +662,9 @@ static void test_blue2d_fused(int n1, int n2, int in_rows, int in_cols, int offy
     RowLoadChirp<T> lp{view, t1.data(), t2.data(), n1};
     RowStoreTiled<T> sp{W1.data(), n1, ltl};
     emu_kernel<RC, false>((n1 + RC::BO * RE - 1) / (RC::BO * RE), lp, sp, twN.data());
-    ColLoadTiled<T> cl{W1.data(), n1, AxisMap{M, n1, 0, 0}, ntiles, log_k};
+    ColLoadTiled<T> cl{W1.data(), n1, AxisMap{M, n1, 0, 0}, ntiles, lay.log_k};
     MidMul<T> mm{MUL_SEPARABLE, 0, t1.data() + n1, t2.data() + n2, 0, N};
-    ColStoreTiledCrop<T> cst{W2.data(), n1, ntiles, log_k};
+    ColStoreTiledCrop<T> cst{W2.data(), n1, ntiles, lay.log_k};
     {
         std::vector<Regs<CC>> regs(CC::NT);
         std::vector<typename LdsType<CC>::type> lds(CC::LDS_ELEMS + 1);
