@@ -682,6 +682,29 @@ int pm_tf_thickness_grad(int32_t dtype, int32_t pol, int64_t K, int64_t L, const
                          const void* n0, int64_t n0_ss, const void* dR, const void* dT, int64_t seed_pstride, int32_t accumulate, void* grad,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Sequential ray trace (csrc/raytrace.hip): prysm/x/raytracing -- spencer_and_murty.raytrace (spencer_and_murty.py:500-622) around
+ * Surface.interact (surfaces.py:1407-1482), with ray_plane_intersect and ray_conic_intersect (intersections.py:21-134),
+ * ConicSeedMixin.intersect, _domain_corridor and _lipschitz_march_solve_s (intersections.py:169-477), newton_raphson_solve_s, refract
+ * and reflect (spencer_and_murty.py:207-306, 424-479) and the conic and even-asphere sags and normals (sags.py:109-121, 413-483).  One
+ * thread per ray walks the J surfaces with the ray in registers.  dtype PM_F32 or PM_F64 is the type of P, S and of the outputs and the
+ * type the kernel computes in.  `table`: DEVICE, J records of PM_RT_RECORD doubles, 8-byte aligned, packed by
+ * prysm_amd/x/raytrace_plan.py (pack_table; the layout is the enum at the top of csrc/raytrace.hip): interaction, shape and its
+ * parameters (c, k, dx, dy, up to 8 even-asphere coefficients), vertex and rotation, the index after the surface, the aperture, the
+ * conic-seed departure band, the first-surface and analytic flags.  n_launch is the index the rays start in; tol_sag the convergence
+ * tolerance on |Z - sag| (resolve_tol_sag: 1e-12 for double, 100 eps for float).  P, S: DEVICE, N x 3, contiguous.
+ * history = 1: P_out, S_out are (J + 1) x N x 3 and OPL_out (J + 1) x N, row 0 the launch (OPL 0), the reference's layout.
+ * history = 0 (not in the reference): P_out, S_out N x 3 -- the last row -- and OPL_out N, the segments' lengths added in surface
+ * order.  status_surface, status_code: N int32 each, the real and imaginary part of the reference's complex status -- the 1-based
+ * surface and PM_RT_* code of a ray's FIRST failure, or J and PM_RT_OK; from the failing surface on the ray's P, S and OPL are NaN.
+ * One launch.  N = 0 or J = 0 returns 0 without a launch (for J = 0 the caller fills row 0 and the status).
+ * prysm_amd/x/raytrace_plan.py is the same arithmetic in numpy. */
+enum { PM_RT_REFLECT = 0, PM_RT_REFRACT = 1, PM_RT_MEASURE = 2 };
+enum { PM_RT_PLANE = 0, PM_RT_CONIC = 1, PM_RT_ASPHERE = 2 };
+enum { PM_RT_OK = 0, PM_RT_NEWTON = 1, PM_RT_CLIP = 2, PM_RT_MISS = -1, PM_RT_TIR = -2 };
+enum { PM_RT_RECORD = 48, PM_RT_MAX_SURFACES = 4096, PM_RT_MAX_COEFS = 8 };
+int pm_rt_trace(int32_t dtype, int64_t N, int64_t J, const void* table, double n_launch, double tol_sag, int32_t history, const void* P,
+                const void* S, void* P_out, void* S_out, void* OPL_out, void* status_surface, void* status_code, void* stream);
+
 /* Segmented apertures (csrc/segmented.hip): CompositeHexagonalAperture.compose_opd (prysm/segmented.py:178-285) and its adjoint.
  * The grid is rows x cols REAL points (dtype PM_F32 / PM_F64, computed in that precision); x, y are the aperture's DEVICE coordinate
  * arrays.  `plan` is a DEVICE array of nseg 80-byte segment records built by prysm_amd/segmented.py (struct pm::SegDesc: int32 y0, x0,

@@ -41,6 +41,10 @@ PM_ACT_TANH, PM_ACT_ARCTAN, PM_ACT_SOFTPLUS, PM_ACT_SIGMOID = 0, 1, 2, 3
 PM_GRAD_FORWARD_X, PM_GRAD_ADJOINT_X, PM_GRAD_FORWARD_Y, PM_GRAD_ADJOINT_Y = 0, 1, 2, 3
 PM_TF_S, PM_TF_P, PM_TF_BOTH = 0, 1, 2
 PM_TF_T_STACK, PM_TF_T_THINFILM = 0, 1
+PM_RT_REFLECT, PM_RT_REFRACT, PM_RT_MEASURE = 0, 1, 2
+PM_RT_PLANE, PM_RT_CONIC, PM_RT_ASPHERE = 0, 1, 2
+PM_RT_OK, PM_RT_NEWTON, PM_RT_CLIP, PM_RT_MISS, PM_RT_TIR = 0, 1, 2, -1, -2
+PM_RT_RECORD, PM_RT_MAX_SURFACES, PM_RT_MAX_COEFS = 48, 4096, 8
 
 c_i32, c_i64, c_f64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
 
@@ -165,6 +169,7 @@ SIGNATURES = {
     'pm_tf_thickness_grad_workspace': (c_sz, [c_i32, c_i32, c_i64, c_i64]),
     'pm_tf_thickness_grad': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
                              c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_sz, c_vp]),
+    'pm_rt_trace': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_f64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'pm_segment_plan_check': (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64]),
     'pm_segment_compose': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                    c_vp, c_i32, c_vp, c_vp]),

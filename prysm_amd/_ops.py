@@ -905,6 +905,34 @@ def tf_thickness_grad(op, pol, dR=None, dT=None, grad=None):
     return grad
 
 
+# --------------------------------------------------------------------------- ray trace (csrc/raytrace.hip)
+
+def rt_trace(table, n_launch, tol_sag, P, S, history=True):
+    """pm_rt_trace: N rays P, S ((N, 3) device tensors of float32 or float64, any strides) through the J records of `table` (a device
+    tensor of float64, x/raytrace_plan.py pack_table).  Returns P, S ((J + 1, N, 3), or (N, 3) without history), OPL ((J + 1, N) or
+    (N,)) and the int32 status tensors surface and code.  One launch; nothing is read on the host and nothing copied to the device."""
+    dev = L.device()
+    if P.dtype not in (torch.float32, torch.float64) or S.dtype != P.dtype:
+        raise TypeError(f'rays are float32 or float64 and P and S of one type, got {P.dtype} and {S.dtype}')
+    if P.dim() != 2 or P.shape[1] != 3 or S.shape != P.shape:
+        raise ValueError(f'P and S are (N, 3), got {tuple(P.shape)} and {tuple(S.shape)}')
+    if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != L.PM_RT_RECORD or not table.is_contiguous():
+        raise ValueError('the surface table is a contiguous (J, PM_RT_RECORD) float64 tensor')
+    P, S = P.contiguous(), S.contiguous()
+    N, J = P.shape[0], table.shape[0]
+    rows = (J + 1,) if history else ()
+    Po, So = torch.empty(rows + (N, 3), dtype=P.dtype, device=dev), torch.empty(rows + (N, 3), dtype=P.dtype, device=dev)
+    Oo = torch.empty(rows + (N,), dtype=P.dtype, device=dev)
+    surface, code = torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev)
+    if J == 0:      # no surface: the launch is the result
+        (Po[0] if history else Po).copy_(P), (So[0] if history else So).copy_(S)
+        Oo.zero_(), surface.zero_(), code.zero_()
+    L.check(L.load().pm_rt_trace(L.PM_F32 if P.dtype == torch.float32 else L.PM_F64, N, J, L.ptr(table), float(n_launch), float(tol_sag),
+                                 int(bool(history)), L.ptr(P), L.ptr(S), L.ptr(Po), L.ptr(So), L.ptr(Oo), L.ptr(surface), L.ptr(code),
+                                 L.stream_ptr()))
+    return Po, So, Oo, surface, code
+
+
 def ceil_half(d):
     return math.ceil(d / 2)
 

@@ -2,7 +2,9 @@
 
 make_xy_grid, cart_to_polar and polar_to_cart are one launch each, both outputs from one kernel (csrc/geometry.hip); the two view
 helpers are host logic on tensors.  Grids come back in config.precision, conversions in the inputs' precision (float32 when every
-input is float32, float64 otherwise).  The rest of the reference module (homographies, warps, resampling, quadratures) is not here.
+input is float32, float64 otherwise).  The pose helpers of the ray trace -- promote_3d_point, coerce_3d_rotation,
+apply_tilt_decenter and make_rotation_matrix (coordinates.py:168-266, 381-429) -- are host code on numpy: a Surface's pose is built on
+the host.  The rest of the reference module (homographies, warps, resampling, quadratures) is not here.
 """
 import numpy as np
 import torch
@@ -11,7 +13,8 @@ from . import _lib as L
 from .conf import config
 from .geometry_plan import grid_spacing
 
-__all__ = ['make_xy_grid', 'cart_to_polar', 'polar_to_cart', 'optimize_xy_separable', 'broadcast_1d_to_2d']
+__all__ = ['make_xy_grid', 'cart_to_polar', 'polar_to_cart', 'optimize_xy_separable', 'broadcast_1d_to_2d', 'promote_3d_point',
+           'coerce_3d_rotation', 'apply_tilt_decenter', 'make_rotation_matrix']
 
 
 def _real_dtype(*arrays, what='coordinates'):
@@ -99,3 +102,45 @@ def polar_to_cart(rho, phi):
     x, y = torch.empty(shape, dtype=dt, device=r.device), torch.empty(shape, dtype=dt, device=r.device)
     L.check(L.load().pm_polar_to_cart(_code(dt), x.numel(), L.ptr(r), L.ptr(p), L.ptr(x), L.ptr(y), L.stream_ptr()))
     return x, y
+
+
+# --------------------------------------------------------------------------- poses (host, numpy)
+
+def promote_3d_point(P, dtype=None):
+    """A point from a z, a (y, z) or an (x, y, z): a scalar is z, a sequence fills the coordinates from the right; more than three
+    (or no) values are a ValueError"""
+    coords = list(P) if hasattr(P, '__iter__') else [P]
+    if len(coords) not in (1, 2, 3):
+        raise ValueError('P must contain one to three coordinates')
+    return np.array([0] * (3 - len(coords)) + coords, dtype=config.precision if dtype is None else dtype)
+
+
+def make_rotation_matrix(zyx, radians=False):
+    """The rotation Rx(a) Ry(b) Rz(g) from up to three angles given in the order (g about z, b about y, a about x), missing ones zero;
+    degrees unless `radians`.  Written out as one matrix from the six sines and cosines."""
+    g, b, a = (tuple(float(v) for v in zyx) + (0.0, 0.0, 0.0))[:3]
+    if not radians:
+        g, b, a = np.radians(g), np.radians(b), np.radians(a)
+    sa, ca, sb, cb, sg, cg = np.sin(a), np.cos(a), np.sin(b), np.cos(b), np.sin(g), np.cos(g)
+    return np.array([[cb * cg, -cb * sg, sb],
+                     [sa * sb * cg + ca * sg, ca * cg - sa * sb * sg, -sa * cb],
+                     [sa * sg - ca * sb * cg, ca * sb * sg + sa * cg, ca * cb]])
+
+
+def coerce_3d_rotation(R):
+    """a list or tuple is (z, y, x) angles in degrees and becomes their matrix; a matrix, or None for no rotation, passes through"""
+    return make_rotation_matrix(R) if type(R) in (list, tuple) else R
+
+
+def apply_tilt_decenter(P, R, tilt=None, decenter=None, tilt_radians=False, dtype=None):
+    """The pose (P, R) moved by `decenter` (three values, else a ValueError) and turned by `tilt` ((z, y, x) angles, applied on the right
+    of R).  R None is no rotation and stays None when there is no tilt."""
+    if decenter is not None:
+        shift = np.asarray(decenter, dtype=config.precision if dtype is None else dtype)
+        if shift.shape != (3,):
+            raise ValueError(f'decenter must be a length-3 vector, got shape {shift.shape}')
+        P = P + shift
+    if tilt is None:
+        return P, R
+    turn = make_rotation_matrix(tilt, radians=tilt_radians)
+    return P, (turn if R is None else R @ turn)
