@@ -705,6 +705,43 @@ enum { PM_RT_RECORD = 48, PM_RT_MAX_SURFACES = 4096, PM_RT_MAX_COEFS = 8 };
 int pm_rt_trace(int32_t dtype, int64_t N, int64_t J, const void* table, double n_launch, double tol_sag, int32_t history, const void* P,
                 const void* S, void* P_out, void* S_out, void* OPL_out, void* status_surface, void* status_code, void* stream);
 
+/* Step-index fibre LP modes without a stored basis (csrc/fibers.hip; prysm/x/fibers.py).  Points are npts contiguous REAL polar
+ * coordinates r, t (dtype PM_F32 / PM_F64, computed in that precision); a is the core radius.  `table` is a DEVICE array of nrec records
+ * built by prysm_amd/x/fibers_plan.py mode_table (struct pm::FRec: T U, W, invJ, invK; int32 l, slot_cos, slot_sin, flags -- 32 bytes
+ * for PM_F32, 48 for PM_F64), one per radial function (|l|, m), sorted by |l|: U = V sqrt(1 - b), W = V sqrt(b), the normalisers
+ * 1 / J_l(U) and 1 / (e^W K_l(W)) evaluated on the host AT the U, W the record holds, and the output slots in [0, nmodes) of the
+ * cosine (+l, or l = 0) and sine (-l) mode (-1: not wanted).  The radial value is J_l(U r/a) / J_l(U) for r <= a, else
+ * K_l(W r/a) / K_l(W) (compute_LP_modes, fibers.py:343-421); flags = 1 takes r (1/a) < 1 as the core (smf_mode_field, fibers.py:424-459,
+ * whose J1 / K1 normalisers the record then holds).  J_l and K_l are the unit's own (the device library has no K_n and no J_n usable
+ * below x = n).  prysm_amd/x/fibers_plan.py is the same arithmetic in numpy. */
+
+/* out (nmodes, npts): every mode of the table, one launch -- compute_LP_modes (fibers.py:343-421) and smf_mode_field. */
+int pm_fiber_modes(int32_t dtype, int64_t npts, const void* r, const void* t, double a, const void* table, int64_t nrec, int64_t nmodes,
+                   void* out, void* stream);
+
+/* out[b][p] (+)= sum_k coefs[b][k] mode_k[p] for batch coefficient vectors (coefs: DEVICE, batch x nmodes, read at launch time, so a
+ * captured graph uses their current values), the modes evaluated once per point for every 8 vectors and never stored: the field at a
+ * multimode fibre's exit face.  Complex coefficients are two real vectors (re, im) and come out as two planes.  Not in the reference
+ * (it sums a stored compute_LP_modes dictionary). */
+int pm_fiber_sum(int32_t dtype, int64_t npts, const void* r, const void* t, double a, const void* table, int64_t nrec, int64_t nmodes,
+                 int64_t batch, const void* coefs, int32_t accumulate, void* out, void* stream);
+
+/* out[b][k] = sum_p g[b][p] mode_k[p] for batch real vectors g (a complex incident field is Re E, Im E): the sums multimode_coupling
+ * (fibers.py:551-588) forms from its stored modes, one per mode_overlap_integral call.  g = NULL (batch 1): sum_p mode_k[p]^2, the
+ * other factor of its denominators.  Deterministic: one partial per (workgroup, output) in the workspace, summed in a fixed order by
+ * a second launch; no atomics.  More modes than a workgroup has accumulators for (2048 in PM_F64) is PM_ERR_UNSUPPORTED. */
+size_t pm_fiber_project_workspace(int32_t dtype, int64_t npts, int64_t nmodes, int64_t batch);
+int pm_fiber_project(int32_t dtype, int64_t npts, const void* r, const void* t, double a, const void* table, int64_t nrec, int64_t nmodes,
+                     int64_t batch, const void* g, void* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* mode_overlap_integral (fibers.py:505-548) in one pass over both fields: out (DEVICE, 5 reals of dtype PM_F32 / PM_F64) =
+ * Re S, Im S, I1, I2, eta with S = sum E1 conj(E2), I1 = sum |E1|^2, I2 = sum |E2|^2, eta = |S|^2 / (I1 I2).  e1_complex / e2_complex:
+ * the field is npts interleaved (re, im) pairs, aligned to the pair; else npts reals.  Nothing is read back, so the call can be
+ * captured.  Deterministic as above (workspace: pm_overlap_workspace). */
+size_t pm_overlap_workspace(int32_t dtype, int64_t npts);
+int pm_overlap(int32_t dtype, int64_t npts, const void* e1, int32_t e1_complex, const void* e2, int32_t e2_complex, void* out,
+               void* workspace, size_t workspace_bytes, void* stream);
+
 /* Segmented apertures (csrc/segmented.hip): CompositeHexagonalAperture.compose_opd (prysm/segmented.py:178-285) and its adjoint.
  * The grid is rows x cols REAL points (dtype PM_F32 / PM_F64, computed in that precision); x, y are the aperture's DEVICE coordinate
  * arrays.  `plan` is a DEVICE array of nseg 80-byte segment records built by prysm_amd/segmented.py (struct pm::SegDesc: int32 y0, x0,

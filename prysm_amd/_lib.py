@@ -170,6 +170,12 @@ SIGNATURES = {
     'pm_tf_thickness_grad': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
                              c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_sz, c_vp]),
     'pm_rt_trace': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_f64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'pm_fiber_modes': (c_i32, [c_i32, c_i64, c_vp, c_vp, c_f64, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    'pm_fiber_sum': (c_i32, [c_i32, c_i64, c_vp, c_vp, c_f64, c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp]),
+    'pm_fiber_project_workspace': (c_sz, [c_i32, c_i64, c_i64, c_i64]),
+    'pm_fiber_project': (c_i32, [c_i32, c_i64, c_vp, c_vp, c_f64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'pm_overlap_workspace': (c_sz, [c_i32, c_i64]),
+    'pm_overlap': (c_i32, [c_i32, c_i64, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_sz, c_vp]),
     'pm_segment_plan_check': (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64]),
     'pm_segment_compose': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                    c_vp, c_i32, c_vp, c_vp]),
