@@ -96,6 +96,8 @@ NMS20 = [(n, m) for n in range(21) for m in range(-n, n + 1, 2)]
 
 
 def test_1024_against_the_numpy_walk():
+    """1024^2 points are exactly the projection's cap of 1024 workgroups of 1024 points, so every workgroup's loop runs once here; the
+    strided case lives in tests/test_gpu_modal_scale.py."""
     from prysm_amd import polynomials as P
     from prysm_amd.polynomials import zernike as Z
     from prysm_amd.polynomials.zernike_plan import evaluate, plan
