@@ -742,6 +742,94 @@ size_t pm_overlap_workspace(int32_t dtype, int64_t npts);
 int pm_overlap(int32_t dtype, int64_t npts, const void* e1, int32_t e1_complex, const void* e2, int32_t e2_complex, void* out,
                void* workspace, size_t workspace_bytes, void* stream);
 
+/* The image chain (csrc/imagechain.hip): prysm/objects.py, prysm/degradations.py, prysm/psf.py and uniform_cart_to_polar of
+ * prysm/coordinates.py.  REAL working precision, PM_F32 or PM_F64; every array is on the DEVICE, the small records are HOST structs read
+ * at call time.  The unit is compiled without multiply-add contraction; prysm_amd/imagechain_plan.py is the same arithmetic in numpy. */
+enum { PM_OBJECT_SLIT = 0, PM_OBJECT_PINHOLE = 1, PM_OBJECT_SIEMENSSTAR = 2, PM_OBJECT_TILTEDSQUARE = 3, PM_OBJECT_SLANTEDEDGE = 4 };
+enum { PM_OBJECT_SLIT_X = 1, PM_OBJECT_SLIT_Y = 2, PM_OBJECT_BINARY = 4, PM_OBJECT_CROSSED = 8 };
+/* kind, flags and parameters p (doubles, rounded once to the working precision):
+ *   SLIT          flags SLIT_X / SLIT_Y: which slits; p = half width in x, in y.                          out: mask (1 byte per sample)
+ *   PINHOLE       p = radius.                                                                             out: mask
+ *   SIEMENSSTAR   flags BINARY; p = spokes / 2, contrast, outer radius, inner radius, background value (0 or 1), bottom, top
+ *   TILTEDSQUARE  p = cos(angle), sin(angle), radius, value inside, value outside
+ *   SLANTEDEDGE   flags CROSSED (square grids only); p = cos(angle), sin(angle), value where xp > 0, value elsewhere */
+typedef struct pm_object {
+    int32_t kind, flags;
+    double p[8];
+} pm_object;
+
+/* slit, pinhole, siemensstar, tiltedsquare, slantededge (objects.py:8-37, 91-107, 130-181, 184-224, 227-258): out (ny x nx, rows out_ld
+ * apart; uint8 0 / 1 for the masks, dtype otherwise), one launch, each sample stored once.  coords as pm_sdf_render: PM_COORDS_GRID
+ * (a, b unused; x = (col - nx / 2) dx, y = (row - ny / 2) dx, make_xy_grid's elements), PM_COORDS_SEPARABLE (a = x, nx values; b = y, ny
+ * values ldb elements apart) or PM_COORDS_POINTWISE (a, b: ny x nx arrays, rows lda / ldb apart).  polar != 0 (POINTWISE, pinhole and
+ * Siemens star): a, b hold (r, t) as the reference takes them (b may be NULL for the pinhole); otherwise those two targets form
+ * r = hypot(x, y), t = atan2(y, x) in registers.  The crossed edge evaluates the edge at (i, j), (j, N-1-i), (N-1-i, N-1-j), (N-1-j, i). */
+int pm_object_render(int32_t dtype, int32_t coords, int32_t polar, int64_t ny, int64_t nx, const void* a, int64_t lda, const void* b,
+                     int64_t ldb, double dx, const pm_object* obj, void* out, int64_t out_ld, void* stream);
+
+/* Analytic transfer functions and their product.  A record is one factor:
+ *   SINC_X / SINC_Y   sinc(f p0)                     pixel_ft (detector.py:174-194), smear_ft (degradations.py:7-39)
+ *   COS_X / COS_Y     cos(p0 f)                      olpf_ft (detector.py:151-171), p0 = 2 width
+ *   GAUSS_R           exp(-2 (p0 fr)^2)              jitter_ft (degradations.py:42-59), p0 = pi scale
+ *   JINC_R            jinc(fr p0)                    pinhole_ft (objects.py:110-127), p0 = 2 pi radius
+ *   AIRY_FT_R         2/pi (acos s - s sqrt(1 - s^2)), s = min(|fr| / p0, 1)      airydisk_ft (psf.py:268-292), p0 = 1 / (wavelength fno)
+ *   AIRY_R / AIRY_EFIELD_R   |2 jinc(u)|^2 / 2 jinc(u), u = r pi / p0 / p1        airydisk, airydisk_efield (psf.py:240-265), p = wavelength, fno
+ *   SLIT_FT           slit_ft (objects.py:40-88): flags PM_OBJECT_SLIT_X / _Y, p = width_x, width_y; with both, the grid lengths are
+ *                     1 / (f[1] - f[0]) of each axis and the bands test the other frequency == 0 exactly
+ *   MAP_REAL / MAP_COMPLEX   a user array (ptr, rows ld apart; dtype, or interleaved pairs of it) multiplied in
+ * jinc = J1(x) / x from the Chebyshev tables of csrc/fibers_coefs.h (mathops.py:232-259 divides scipy's j1). */
+enum { PM_TFP_SINC_X = 0, PM_TFP_SINC_Y = 1, PM_TFP_COS_X = 2, PM_TFP_COS_Y = 3, PM_TFP_GAUSS_R = 4, PM_TFP_JINC_R = 5, PM_TFP_AIRY_FT_R = 6,
+       PM_TFP_SLIT_FT = 7, PM_TFP_MAP_REAL = 8, PM_TFP_MAP_COMPLEX = 9, PM_TFP_AIRY_R = 10, PM_TFP_AIRY_EFIELD_R = 11 };
+enum { PM_FREQ_GRID = 0, PM_FREQ_VECTORS = 1, PM_FREQ_POINTWISE = 2 };
+enum { PM_TF_MAX_RECORDS = 16 };
+typedef struct pm_tf_record {
+    int32_t kind, flags;
+    int64_t ld;
+    const void* ptr;
+    double p[4];
+} pm_tf_record;
+/* Where the frequencies of sample (row, col) come from.  GRID: the bin's integer times 1 / (n dx) in double, rounded once to dtype --
+ * fttools.forward_ft_unit(dx, n, shift) (fttools.py:128-152), even and odd n.  VECTORS: fx (n values), fy (m values, ldy elements
+ * apart).  POINTWISE: m x n arrays fx, fy and / or fr (rows ldx, ldy, ldr apart; fr = hypot(fx, fy) where fr is NULL).
+ * shift != 0: the inputs (frequencies and maps) have their origin at the centre, [m / 2, n / 2]; the output never has. */
+typedef struct pm_tf_freq {
+    int32_t mode, shift;
+    double dx;
+    const void* fx;
+    const void* fy;
+    const void* fr;
+    int64_t ldx, ldy, ldr;
+} pm_tf_freq;
+
+/* out (m x n, rows out_ld apart; complex pairs when out_complex, else dtype) = the product of the records, in their order, with its
+ * origin at [0, 0]: out[i, j] = product at input index ((i + m / 2) mod m, (j + n / 2) mod n) when freq->shift, an index rotation
+ * in the kernel.  One launch, each sample stored once: what convolution.apply_transfer_functions (convolution.py:34-113) forms map by map. */
+int pm_tf_product(int32_t dtype, int64_t m, int64_t n, const pm_tf_freq* freq, const pm_tf_record* records, int64_t nrec, int32_t out_complex,
+                  void* out, int64_t out_ld, void* stream);
+
+/* uniform_cart_to_polar (coordinates.py:269-316): out[i, j] = data interpolated bilinearly at (x, y) = rho[j] (cos phi[i], sin phi[i]),
+ * data sampled on the ascending regular axes x (nx values) and y (ny values) whose spacings x_step, y_step seed the cell search; 0
+ * outside [min, max] of either axis, the boundary inside (scipy's RegularGridInterpolator, linear, fill_value 0).  One gather launch. */
+int pm_polar_resample(int32_t dtype, int64_t ny, int64_t nx, const void* x, const void* y, double x_step, double y_step, const void* rho,
+                      const void* phi, const void* data, int64_t data_ld, void* out, int64_t out_ld, void* stream);
+
+/* centroid (psf.py:174-203; scipy's center_of_mass): out (DEVICE, 2 doubles) = sum(row d) / sum(d), sum(col d) / sum(d) over an m x n
+ * array, summed in double.  Two launches, one partial triple per workgroup in the workspace folded in a fixed order: no atomics, the
+ * same bits every run, nothing read on the host. */
+size_t pm_centroid_workspace(int64_t m, int64_t n);
+int pm_centroid(int32_t dtype, int64_t m, int64_t n, const void* data, int64_t ld, void* out, void* workspace, size_t workspace_bytes,
+                void* stream);
+
+/* estimate_size after its resample (psf.py:63-90): the maximum of the polar map (rows x cols), the threshold hm = value * max in dtype
+ * (relative != 0) or value, per row -- one wavefront each -- the first (last = 0) or last index where polar > hm changes and the radius
+ * r[i] + frac (r[i+1] - r[i]) there, then out (DEVICE, 2 doubles) = the mean over the rows that cross, and their count.  Four launches
+ * (maximum partials, its fold, crossings, mean), deterministic as above.  pm_psf_size_groups: the workgroups of the crossing launch,
+ * four rows each per trip. */
+size_t pm_psf_size_workspace(int64_t rows);
+int64_t pm_psf_size_groups(int64_t rows);
+int pm_psf_size(int32_t dtype, int64_t rows, int64_t cols, const void* polar, int64_t ld, const void* r, int32_t relative, double value,
+                int32_t last, void* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Segmented apertures (csrc/segmented.hip): CompositeHexagonalAperture.compose_opd (prysm/segmented.py:178-285) and its adjoint.
  * The grid is rows x cols REAL points (dtype PM_F32 / PM_F64, computed in that precision); x, y are the aperture's DEVICE coordinate
  * arrays.  `plan` is a DEVICE array of nseg 80-byte segment records built by prysm_amd/segmented.py (struct pm::SegDesc: int32 y0, x0,

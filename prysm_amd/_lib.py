@@ -45,6 +45,12 @@ PM_RT_REFLECT, PM_RT_REFRACT, PM_RT_MEASURE = 0, 1, 2
 PM_RT_PLANE, PM_RT_CONIC, PM_RT_ASPHERE = 0, 1, 2
 PM_RT_OK, PM_RT_NEWTON, PM_RT_CLIP, PM_RT_MISS, PM_RT_TIR = 0, 1, 2, -1, -2
 PM_RT_RECORD, PM_RT_MAX_SURFACES, PM_RT_MAX_COEFS = 48, 4096, 8
+PM_OBJECT_SLIT, PM_OBJECT_PINHOLE, PM_OBJECT_SIEMENSSTAR, PM_OBJECT_TILTEDSQUARE, PM_OBJECT_SLANTEDEDGE = 0, 1, 2, 3, 4
+PM_OBJECT_SLIT_X, PM_OBJECT_SLIT_Y, PM_OBJECT_BINARY, PM_OBJECT_CROSSED = 1, 2, 4, 8
+(PM_TFP_SINC_X, PM_TFP_SINC_Y, PM_TFP_COS_X, PM_TFP_COS_Y, PM_TFP_GAUSS_R, PM_TFP_JINC_R, PM_TFP_AIRY_FT_R, PM_TFP_SLIT_FT, PM_TFP_MAP_REAL,
+ PM_TFP_MAP_COMPLEX, PM_TFP_AIRY_R, PM_TFP_AIRY_EFIELD_R) = range(12)
+PM_FREQ_GRID, PM_FREQ_VECTORS, PM_FREQ_POINTWISE = 0, 1, 2
+PM_TF_MAX_RECORDS = 16
 
 c_i32, c_i64, c_f64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
 
@@ -63,6 +69,19 @@ class pm_fft2_desc(ctypes.Structure):
         ('batch', c_i64), ('in_bstride', c_i64), ('out_bstride', c_i64), ('mul_bstride', c_i64), ('mul_x_bstride', c_i64),
         ('synth_amp', c_vp), ('synth_amp_dtype', c_i32), ('synth_reserved', c_i32), ('synth_amp_ld', c_i64), ('synth_k', c_f64),
     ]
+
+
+class pm_object(ctypes.Structure):
+    _fields_ = [('kind', c_i32), ('flags', c_i32), ('p', c_f64 * 8)]
+
+
+class pm_tf_record(ctypes.Structure):
+    _fields_ = [('kind', c_i32), ('flags', c_i32), ('ld', c_i64), ('ptr', c_vp), ('p', c_f64 * 4)]
+
+
+class pm_tf_freq(ctypes.Structure):
+    _fields_ = [('mode', c_i32), ('shift', c_i32), ('dx', c_f64), ('fx', c_vp), ('fy', c_vp), ('fr', c_vp), ('ldx', c_i64), ('ldy', c_i64),
+                ('ldr', c_i64)]
 
 
 # name -> (restype, argtypes); tests/test_capi_symbols.py checks this table against include/prysm_amd.h
@@ -176,6 +195,14 @@ SIGNATURES = {
     'pm_fiber_project': (c_i32, [c_i32, c_i64, c_vp, c_vp, c_f64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'pm_overlap_workspace': (c_sz, [c_i32, c_i64]),
     'pm_overlap': (c_i32, [c_i32, c_i64, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_sz, c_vp]),
+    'pm_object_render': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_f64, ctypes.POINTER(pm_object), c_vp, c_i64, c_vp]),
+    'pm_tf_product': (c_i32, [c_i32, c_i64, c_i64, ctypes.POINTER(pm_tf_freq), ctypes.POINTER(pm_tf_record), c_i64, c_i32, c_vp, c_i64, c_vp]),
+    'pm_polar_resample': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_vp, c_f64, c_f64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    'pm_centroid_workspace': (c_sz, [c_i64, c_i64]),
+    'pm_centroid': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    'pm_psf_size_workspace': (c_sz, [c_i64]),
+    'pm_psf_size_groups': (c_i64, [c_i64]),
+    'pm_psf_size': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_sz, c_vp]),
     'pm_segment_plan_check': (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64]),
     'pm_segment_compose': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                    c_vp, c_i32, c_vp, c_vp]),

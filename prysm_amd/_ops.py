@@ -944,3 +944,131 @@ for _name in ('fft2', 'fft2_real', 'pack_amp_opd', 'fft2_mul_ifft2', 'fft1', 'cz
               'quadratic_phase', 'as_tf_vectors', 'outer', 'embed', 'pad_index', 'mdft_basis', 'mdft_basis_grid', 'cgemm', 'cgemm_abs2'):
     globals()[_name] = sequenced(globals()[_name])
 del _name
+
+
+# --------------------------------------------------------------------------- the image chain (csrc/imagechain.hip)
+
+def _rows(t, dtype):
+    """a device tensor as rows with unit element stride: (2-D tensor, elements between its rows).  Strided row views pass as they are."""
+    as_is = (isinstance(t, torch.Tensor) and t.device == L.device() and t.dtype == dtype and t.dim() == 2 and t.stride(1) == 1
+             and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]) and not t.is_conj() and not t.is_neg())
+    if not as_is:
+        t = L.as_device(t, dtype)
+        t = t.reshape(1, -1) if t.dim() < 2 else t.reshape(-1, t.shape[-1])
+    return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def _vector(t, dtype):
+    """a 1-D device tensor and the elements between its values (a column of a 2-D array passes as it is)"""
+    if isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == L.device() and t.dim() == 1 and t.stride(0) >= 1:
+        return t, t.stride(0)
+    t = L.as_device(t, dtype).reshape(-1)
+    return t, 1
+
+
+def object_render(kind, flags, p, dtype, coords, ny, nx, *, a=None, lda=0, b=None, ldb=0, dx=0.0, polar=False):
+    """pm_object_render: a target of kind / flags / parameters p on ny x nx samples; a torch.bool mask for the slit and the pinhole"""
+    from . import imagechain_plan as IP
+    obj = L.pm_object()
+    obj.kind, obj.flags = int(kind), int(flags)
+    for i, v in enumerate(p):
+        obj.p[i] = float(v)
+    odt = torch.bool if kind in (IP.SLIT, IP.PINHOLE) else dtype
+    out = torch.empty((ny, nx), dtype=odt, device=L.device())
+    L.check(L.load().pm_object_render(L.PM_F32 if dtype == torch.float32 else L.PM_F64, coords, int(bool(polar)), ny, nx, L.ptr(a), lda, L.ptr(b),
+                                      ldb, float(dx), ctypes.byref(obj), L.ptr(out), nx, L.stream_ptr()))
+    return out
+
+
+def tf_product(shape, factors, dtype, *, dx=None, shift=False, fx=None, fy=None, fr=None, real_out=False):
+    """pm_tf_product: H (m, n) = the product of the factors -- imagechain_plan Records and arrays of shape (m, n) -- with its origin at
+    [0, 0], in one launch.  dtype: the REAL working precision; H is complex of it unless real_out.  Frequencies: dx (generated), or 1-D
+    fx (n) and fy (m), or 2-D arrays fx / fy / fr of shape (m, n); with shift they and the arrays are centred."""
+    from . import imagechain_plan as IP
+    m, n = int(shape[0]), int(shape[1])
+    cdt = L._COMPLEX_OF[dtype]
+    keep, packed = [], []
+    for f in IP.flatten(factors):
+        if isinstance(f, IP.Record):
+            packed.append(f)
+            continue
+        t = f if isinstance(f, torch.Tensor) else L.as_device(f)
+        cplx = t.is_complex()
+        if tuple(t.shape) != (m, n):
+            t = torch.broadcast_to(L.as_device(t), (m, n)).contiguous()
+        t, ld = _rows(t, cdt if cplx else dtype)
+        if cplx and real_out:
+            raise ValueError('a complex array among the transfer functions needs a complex result')
+        keep.append(t)
+        packed.append((IP.MAP_COMPLEX if cplx else IP.MAP_REAL, ld, t.data_ptr()))
+    table = IP.pack_records(packed)
+    fq = L.pm_tf_freq()
+    fq.shift = int(bool(shift))
+    if dx is not None:
+        fq.mode, fq.dx = L.PM_FREQ_GRID, float(dx)
+    elif all(v is None or (isinstance(v, torch.Tensor) and v.dim() == 1) for v in (fx, fy)) and fr is None:
+        fq.mode = L.PM_FREQ_VECTORS
+        for name, v, length in (('fx', fx, n), ('fy', fy, m)):
+            if v is None:
+                continue
+            t, st = _vector(v, dtype)
+            if t.numel() != length or (name == 'fx' and st != 1):
+                if t.numel() != length:
+                    raise ValueError(f'{name} has {t.numel()} values for an axis of {length}')
+                t, st = t.contiguous(), 1
+            keep.append(t)
+            setattr(fq, name, t.data_ptr())
+            if name == 'fy':
+                fq.ldy = st
+    else:
+        fq.mode = L.PM_FREQ_POINTWISE
+        for name, v, ldn in (('fx', fx, 'ldx'), ('fy', fy, 'ldy'), ('fr', fr, 'ldr')):
+            if v is None:
+                continue
+            t = v if isinstance(v, torch.Tensor) else L.as_device(v, dtype)
+            if tuple(t.shape) != (m, n):
+                t = torch.broadcast_to(t.reshape(1, -1) if t.dim() == 1 else t, (m, n)).contiguous()
+            t, ld = _rows(t, dtype)
+            keep.append(t)
+            setattr(fq, name, t.data_ptr())
+            setattr(fq, ldn, ld)
+    out = torch.empty((m, n), dtype=dtype if real_out else cdt, device=L.device())
+    recs = table.ctypes.data_as(ctypes.POINTER(L.pm_tf_record)) if len(table) else None
+    L.check(L.load().pm_tf_product(L.PM_F32 if dtype == torch.float32 else L.PM_F64, m, n, ctypes.byref(fq), recs, len(table),
+                                   int(not real_out), L.ptr(out), n, L.stream_ptr()))
+    return out
+
+
+def polar_resample(x, y, x_step, y_step, rho, phi, data):
+    """pm_polar_resample: data (ny, nx) on the axes x, y gathered onto rho (nx) x phi (ny), all device tensors of data's dtype"""
+    ny, nx = data.shape
+    out = torch.empty((ny, nx), dtype=data.dtype, device=data.device)
+    L.check(L.load().pm_polar_resample(L.PM_F32 if data.dtype == torch.float32 else L.PM_F64, ny, nx, L.ptr(x), L.ptr(y), float(x_step),
+                                       float(y_step), L.ptr(rho), L.ptr(phi), L.ptr(data), data.stride(0) if ny > 1 else nx, L.ptr(out), nx,
+                                       L.stream_ptr()))
+    return out
+
+
+def centroid(data):
+    """pm_centroid: the centre of mass (row, col) of a 2-D real device tensor as a float64 device 2-vector; nothing is read back"""
+    lib = L.load()
+    m, n = data.shape
+    out = torch.empty(2, dtype=torch.float64, device=data.device)
+    nbytes = lib.pm_centroid_workspace(m, n)
+    ws = L.workspace(nbytes)
+    L.check(lib.pm_centroid(L.PM_F32 if data.dtype == torch.float32 else L.PM_F64, m, n, L.ptr(data), data.stride(0) if m > 1 else n,
+                            L.ptr(out), L.ptr(ws), nbytes, L.stream_ptr()))
+    return out
+
+
+def psf_size(polar, r, relative, value, last):
+    """pm_psf_size: (mean crossing radius, count) of a polar map as a float64 device 2-vector; nothing is read back"""
+    lib = L.load()
+    rows, cols = polar.shape
+    out = torch.empty(2, dtype=torch.float64, device=polar.device)
+    nbytes = lib.pm_psf_size_workspace(rows)
+    ws = L.workspace(nbytes)
+    L.check(lib.pm_psf_size(L.PM_F32 if polar.dtype == torch.float32 else L.PM_F64, rows, cols, L.ptr(polar),
+                            polar.stride(0) if rows > 1 else cols, L.ptr(r), int(relative), float(value), int(last), L.ptr(out), L.ptr(ws),
+                            nbytes, L.stream_ptr()))
+    return out

@@ -1,10 +1,10 @@
 """Coordinate grids and conversions on the device (prysm/coordinates.py:11-125, 344-378).
 
 make_xy_grid, cart_to_polar and polar_to_cart are one launch each, both outputs from one kernel (csrc/geometry.hip); the two view
-helpers are host logic on tensors.  Grids come back in config.precision, conversions in the inputs' precision (float32 when every
+helpers are host logic on tensors.  uniform_cart_to_polar (coordinates.py:269-316) is one gather launch (csrc/imagechain.hip).  Grids come back in config.precision, conversions in the inputs' precision (float32 when every
 input is float32, float64 otherwise).  The pose helpers of the ray trace -- promote_3d_point, coerce_3d_rotation,
 apply_tilt_decenter and make_rotation_matrix (coordinates.py:168-266, 381-429) -- are host code on numpy: a Surface's pose is built on
-the host.  The rest of the reference module (homographies, warps, resampling, quadratures) is not here.
+the host.  The rest of the reference module (homographies, warps, resample_2d, quadratures) is not here.
 """
 import numpy as np
 import torch
@@ -13,7 +13,7 @@ from . import _lib as L
 from .conf import config
 from .geometry_plan import grid_spacing
 
-__all__ = ['make_xy_grid', 'cart_to_polar', 'polar_to_cart', 'optimize_xy_separable', 'broadcast_1d_to_2d', 'promote_3d_point',
+__all__ = ['make_xy_grid', 'cart_to_polar', 'polar_to_cart', 'optimize_xy_separable', 'broadcast_1d_to_2d', 'uniform_cart_to_polar', 'promote_3d_point',
            'coerce_3d_rotation', 'apply_tilt_decenter', 'make_rotation_matrix']
 
 
@@ -102,6 +102,31 @@ def polar_to_cart(rho, phi):
     x, y = torch.empty(shape, dtype=dt, device=r.device), torch.empty(shape, dtype=dt, device=r.device)
     L.check(L.load().pm_polar_to_cart(_code(dt), x.numel(), L.ptr(r), L.ptr(p), L.ptr(x), L.ptr(y), L.stream_ptr()))
     return x, y
+
+
+def uniform_cart_to_polar(x, y, data):
+    """data, sampled uniformly on the sorted 1-D coordinates x (columns) and y (rows), interpolated onto polar coordinates
+    (coordinates.py:269-316): returns (rho, phi, polar) on the device with rho = linspace(0, max|x, y extremes|, len(x)),
+    phi = linspace(0, 2 pi, len(y)) and polar[i, j] the bilinear interpolation at rho[j] (cos phi[i], sin phi[i]) -- scipy's
+    RegularGridInterpolator(method='linear', bounds_error=False, fill_value=0): 0 outside [min, max] of either axis, the boundary
+    inside.  One gather launch (pm_polar_resample); the axes are built on the host from x and y (device vectors are read back, numpy
+    ones are not).  Everything is in the precision of _real_dtype(x, y, data), not in the reference's float64."""
+    from . import _ops
+    from . import imagechain_plan as IP
+    dt = _real_dtype(x, y, data)
+    hx, hy = (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v) for v in (x, y))
+    if hx.ndim != 1 or hy.ndim != 1 or hx.size < 2 or hy.size < 2:
+        raise ValueError('x and y must be sorted 1-D arrays of at least two sample points')
+    npdt = np.float32 if dt == torch.float32 else np.float64
+    hx, hy = hx.astype(npdt), hy.astype(npdt)
+    if tuple(np.shape(data)) != (hy.size, hx.size):
+        raise ValueError(f'data has shape {tuple(np.shape(data))}, the coordinates describe {(hy.size, hx.size)}')
+    rho, phi, _ = IP.polar_axes(hx, hy)
+    d, _ = _ops._rows(data, dt)
+    xd, yd = L.as_device(hx), L.as_device(hy)
+    rd, pd = L.as_device(rho.astype(npdt)), L.as_device(phi.astype(npdt))
+    x_step, y_step = (float(hx[-1]) - float(hx[0])) / (hx.size - 1), (float(hy[-1]) - float(hy[0])) / (hy.size - 1)
+    return rd, pd, _ops.polar_resample(xd, yd, x_step, y_step, rd, pd, d)
 
 
 # --------------------------------------------------------------------------- poses (host, numpy)

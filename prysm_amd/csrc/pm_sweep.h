@@ -6,6 +6,7 @@
 // where there is nothing).  The per-element part comes in two forms, chosen at compile time by the sweep() that is called:
 //     sweep(rows, cols, st, f)          F::point(r, c, column)       one array, grid.z unused (blockIdx.z is not read)
 //     sweep(batch, rows, cols, st, f)   F::point(b, r, c, column)    a stack, member b = blockIdx.z (batch <= 65535)
+//     sweep_heavy(rows, cols, st, f)    as the first, compiled for the 256 threads it is launched with
 #pragma once
 #include "pm_internal.h"
 
@@ -14,7 +15,7 @@ namespace pm {
 struct NoColumn {};
 
 template <bool STACK, typename F>
-__global__ void sweep_kernel(int64_t rows, int64_t cols, const F f) {
+__device__ __forceinline__ void sweep_body(int64_t rows, int64_t cols, const F& f) {
     const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (c >= cols) return;
     if constexpr (STACK) {
@@ -28,12 +29,27 @@ __global__ void sweep_kernel(int64_t rows, int64_t cols, const F f) {
 }
 
 template <bool STACK, typename F>
+__global__ void sweep_kernel(int64_t rows, int64_t cols, const F f) {
+    sweep_body<STACK>(rows, cols, f);
+}
+
+// the same sweep for functors with a long per-element part (csrc/imagechain.hip: transcendental functions in double): the workgroup
+// size is stated, so the register allocator may use what 256 threads leave it instead of spilling at the 128 of an unstated one
+template <bool STACK, typename F>
+__global__ __launch_bounds__(256) void sweep_kernel_heavy(int64_t rows, int64_t cols, const F f) {
+    sweep_body<STACK>(rows, cols, f);
+}
+
+template <bool STACK, bool HEAVY = false, typename F>
 int sweep_launch(int64_t batch, int64_t rows, int64_t cols, hipStream_t st, const F& f) {
     const dim3 block(64, 4);
     const int64_t gx = (cols + block.x - 1) / block.x;
     int64_t gy = (rows + block.y - 1) / block.y;
     if (gy > 65535) gy = 65535;
-    hipLaunchKernelGGL((sweep_kernel<STACK, F>), dim3((unsigned)gx, (unsigned)gy, (unsigned)batch), block, 0, st, rows, cols, f);
+    if constexpr (HEAVY)
+        hipLaunchKernelGGL((sweep_kernel_heavy<STACK, F>), dim3((unsigned)gx, (unsigned)gy, (unsigned)batch), block, 0, st, rows, cols, f);
+    else
+        hipLaunchKernelGGL((sweep_kernel<STACK, F>), dim3((unsigned)gx, (unsigned)gy, (unsigned)batch), block, 0, st, rows, cols, f);
     return int(hipGetLastError());
 }
 
@@ -41,5 +57,7 @@ template <typename F>
 int sweep(int64_t rows, int64_t cols, hipStream_t st, const F& f) { return sweep_launch<false>(1, rows, cols, st, f); }
 template <typename F>
 int sweep(int64_t batch, int64_t rows, int64_t cols, hipStream_t st, const F& f) { return sweep_launch<true>(batch, rows, cols, st, f); }
+template <typename F>
+int sweep_heavy(int64_t rows, int64_t cols, hipStream_t st, const F& f) { return sweep_launch<false, true>(1, rows, cols, st, f); }
 
 }  // namespace pm

@@ -274,6 +274,22 @@ def pixel_ft(fx, fy, width_x, width_y):
     return torch.sinc(fx * width_x) * torch.sinc(fy * width_y)
 
 
+def _olpf_spec(width_x, width_y):
+    """The deferred form of olpf_ft for convolution.apply_transfer_functions / transfer_function: records only, no device work."""
+    from .imagechain_plan import olpf_spec
+    return olpf_spec(width_x, width_y)
+
+
+def _pixel_spec(width_x, width_y):
+    """The deferred form of pixel_ft for convolution.apply_transfer_functions / transfer_function: records only, no device work."""
+    from .imagechain_plan import pixel_spec
+    return pixel_spec(width_x, width_y)
+
+
+olpf_ft.spec = _olpf_spec
+pixel_ft.spec = _pixel_spec
+
+
 def pixel(x, y, width_x, width_y):
     """Spatial representation of a pixel (detector.py:197-219): a torch.bool mask of |x| <= wx / 2 and |y| <= wy / 2."""
     dt = _real_dtype(x, y, what='coordinates')
