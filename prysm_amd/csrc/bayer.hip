@@ -20,7 +20,8 @@
 //  - pm_bayer_weave / pm_bayer_deinterlace / pm_bayer_assemble / pm_bayer_scale: row sweeps (pm_sweep.h: 64 adjacent columns per wave,
 //    64 x 4 threads, threads striding down the rows) in its stacked form, grid.z the member of a stack.
 //  - pm_bayer_class_max: the maxima of the parity classes of a mosaic or of the channels of an RGB image, two launches (partials per
-//    workgroup, then one workgroup), comparisons only: no atomics, deterministic, NaN propagates as numpy's max does.
+//    workgroup, then one workgroup; both stages: pm_reduce.h), comparisons only: no atomics, deterministic, NaN propagates as numpy's
+//    max does.
 //
 // prysm_amd/bayer_plan.py is this file in numpy.  The unit is compiled with -ffp-contract=off (csrc/Makefile) so that every product and
 // sum is rounded by itself, as numpy does.
@@ -28,6 +29,7 @@
 #include <cmath>
 
 #include "pm_entry.h"
+#include "pm_reduce.h"
 #include "pm_sweep.h"
 
 namespace pm {
@@ -204,10 +206,6 @@ struct Assemble {
     }
 };
 
-// numpy's max: NaN wins
-template <typename T>
-__device__ __forceinline__ T nanmax(T a, T b) { return (a != a || a > b) ? a : b; }
-
 // The class of element (r, c): mosaic (nclass 4) 2 * (r & 1) + (c & 1); RGB rows of 3 n values (nclass 3) c % 3.
 __device__ __forceinline__ int class_of(int nclass, int64_t r, int64_t c) { return nclass == 4 ? int(r & 1) * 2 + int(c & 1) : int(c % 3); }
 
@@ -215,53 +213,34 @@ __device__ __forceinline__ int class_of(int nclass, int64_t r, int64_t c) { retu
 template <typename T>
 __global__ __launch_bounds__(256) void class_max_kernel(int nclass, int64_t batch, int64_t rows, int64_t cols, const T* __restrict__ in,
                                                         int64_t ld, int64_t bs, double* __restrict__ partial) {
-    __shared__ T red[4][256];
-    const int tid = threadIdx.y * 64 + threadIdx.x;
     const int64_t c = int64_t(blockIdx.x) * 64 + threadIdx.x;
     T a0 = -INFINITY, a1 = -INFINITY;      // even rows, odd rows
     if (c < cols)
         for (int64_t b = 0; b < batch; ++b)
             for (int64_t r = int64_t(blockIdx.y) * 4 + threadIdx.y; r < rows; r += int64_t(gridDim.y) * 4) {
                 const T v = in[b * bs + r * ld + c];
-                if (r & 1) a1 = nanmax(a1, v);
-                else a0 = nanmax(a0, v);
+                if (r & 1) a1 = FoldNanMax::of(a1, v);      // numpy's max: NaN wins
+                else a0 = FoldNanMax::of(a0, v);
             }
     const int k0 = class_of(nclass, 0, c), k1 = class_of(nclass, 1, c);
+    T a[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         T v = -INFINITY;
-        if (k == k0) v = nanmax(v, a0);
-        if (k == k1) v = nanmax(v, a1);
-        red[k][tid] = v;
+        if (k == k0) v = FoldNanMax::of(v, a0);
+        if (k == k1) v = FoldNanMax::of(v, a1);
+        a[k] = v;
     }
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) red[k][tid] = nanmax(red[k][tid], red[k][tid + s]);
-        __syncthreads();
-    }
-    if (tid < 4) partial[(int64_t(blockIdx.y) * gridDim.x + blockIdx.x) * 4 + tid] = double(red[tid][0]);
+    wg_fold<256, FoldNanMax>(int(threadIdx.y * 64 + threadIdx.x), a, partial + (int64_t(blockIdx.y) * gridDim.x + blockIdx.x) * 4);
 }
 
 // stage 2: one workgroup
 __global__ __launch_bounds__(256) void class_max_final_kernel(int64_t nparts, const double* __restrict__ partial, double* __restrict__ out) {
-    __shared__ double red[4][256];
-    const int tid = threadIdx.x;
-    double a[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    for (int64_t i = tid; i < nparts; i += 256)
+    double a[4];
+    fold_partials<256, FoldNanMax>(threadIdx.x, nparts, partial, -INFINITY, a);
+    if (threadIdx.x == 0)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) a[k] = nanmax(a[k], partial[i * 4 + k]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) red[k][tid] = a[k];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) red[k][tid] = nanmax(red[k][tid], red[k][tid + s]);
-        __syncthreads();
-    }
-    if (tid < 4) out[tid] = red[tid][0];
+        for (int k = 0; k < 4; ++k) out[k] = a[k];
 }
 
 // In place: element (r, c) times the gain of its class.  With `safe` the gains are first divided by the reference's ratio, formed in T

@@ -2,9 +2,10 @@
 //     EE(r) = r * dnx * dny * sum_ij MTF[i][j] * J1(2 pi r nu_ij) / nu_ij,     nu = hypot of the FFT-centred frequency grid
 // and the adjoint's MTF-plane gradient  mtf_bar[i][j] = sum_r ee_bar_r * r * J1(2 pi r nu_ij) / nu_ij * dnx * dny.
 // HBM bound on the MTF read (one pass serves up to 8 radii); the Bessel function is evaluated in fp64 for both precisions and the
-// sums are accumulated in fp64 in a fixed order (fixed grid, tree reduction, second kernel over the per-workgroup partials), so
-// results are reproducible run to run.
+// sums are accumulated in fp64 in a fixed order (fixed grid, tree reduction, second kernel over the per-workgroup partials:
+// pm_reduce.h fold_partials), so results are reproducible run to run.
 #include "pm_entry.h"
+#include "pm_reduce.h"
 
 namespace pm {
 
@@ -63,19 +64,12 @@ __global__ void __launch_bounds__(kEeThreads) ee_reduce_kernel(int64_t rows, int
 
 // out[r] = radius_r * dnx * dny * sum over the workgroup partials (one workgroup, fixed order)
 __global__ void __launch_bounds__(kEeThreads) ee_final_kernel(const double* partial, int nblocks, EeRadii rr, int nrad, double cell, double* out) {
-    __shared__ double red[kEeMaxRadii][kEeThreads];
-    for (int r = 0; r < kEeMaxRadii; ++r) {
-        double v = 0.0;
-        for (int b = threadIdx.x; b < nblocks; b += kEeThreads) v += partial[int64_t(b) * kEeMaxRadii + r];
-        red[r][threadIdx.x] = v;
-    }
-    __syncthreads();
-    for (int s = kEeThreads / 2; s > 0; s >>= 1) {
-        if (int(threadIdx.x) < s)
-            for (int r = 0; r < kEeMaxRadii; ++r) red[r][threadIdx.x] += red[r][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (int(threadIdx.x) < nrad) out[threadIdx.x] = rr.r[threadIdx.x] * red[threadIdx.x][0] * cell;
+    double sum[kEeMaxRadii];
+    fold_partials<kEeThreads, FoldSum>(threadIdx.x, nblocks, partial, 0.0, sum);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int r = 0; r < kEeMaxRadii; ++r)
+            if (r < nrad) out[r] = rr.r[r] * sum[r] * cell;
 }
 
 template <typename T>
@@ -109,8 +103,7 @@ int pm_encircled_energy(int32_t dtype, int64_t rows, int64_t cols, const void* m
         return fail(PM_ERR_WORKSPACE, "pm_encircled_energy: workspace of %zu bytes required", pm_encircled_energy_workspace());
     hipStream_t st = PM_STREAM(stream);
     double* partial = static_cast<double*>(workspace);
-    int64_t nb = (rows * cols + kEeThreads - 1) / kEeThreads;
-    if (nb > kEeBlocks) nb = kEeBlocks;
+    const int nb = reduce_groups(rows * cols, kEeThreads, kEeBlocks);
     const double cell = df * df;   // dnx * dny of the square frequency grid (otf.py:342)
     return by_cdtype(dtype, "pm_encircled_energy", [&](auto real) {
         using T = decltype(real);
@@ -122,7 +115,7 @@ int pm_encircled_energy(int32_t dtype, int64_t rows, int64_t cols, const void* m
                 rr.w[i] = 0.0;
             }
             hipLaunchKernelGGL(ee_reduce_kernel<T>, dim3(unsigned(nb)), dim3(kEeThreads), 0, st, rows, cols, static_cast<const T*>(mtf), mtf_ld, df, rr, nr, partial);
-            hipLaunchKernelGGL(ee_final_kernel, dim3(1), dim3(kEeThreads), 0, st, partial, int(nb), rr, nr, cell, out + r0);
+            hipLaunchKernelGGL(ee_final_kernel, dim3(1), dim3(kEeThreads), 0, st, partial, nb, rr, nr, cell, out + r0);
         }
         return int(hipGetLastError());
     });

@@ -25,6 +25,7 @@
 
 #include "fibers_coefs.h"
 #include "modal_tile.h"
+#include "pm_math.h"
 
 namespace pm {
 namespace {
@@ -40,14 +41,6 @@ struct FRec {
 };
 static_assert(sizeof(FRec<float>) == 32 && sizeof(FRec<double>) == 48, "FRec layout is shared with fibers_plan.record_dtype");
 
-__device__ __forceinline__ float exp_(float x) { return expf(x); }
-__device__ __forceinline__ double exp_(double x) { return exp(x); }
-__device__ __forceinline__ float log_(float x) { return logf(x); }
-__device__ __forceinline__ double log_(double x) { return log(x); }
-__device__ __forceinline__ float sqrt_(float x) { return sqrtf(x); }
-__device__ __forceinline__ double sqrt_(double x) { return sqrt(x); }
-__device__ __forceinline__ float abs_(float x) { return fabsf(x); }
-__device__ __forceinline__ double abs_(double x) { return fabs(x); }
 template <typename T>
 __device__ __forceinline__ T eps_() {
     return sizeof(T) == 4 ? T(1.1920928955078125e-07) : T(2.220446049250313e-16);

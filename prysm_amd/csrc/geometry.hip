@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "pm_entry.h"
+#include "pm_math.h"
 
 namespace pm {
 namespace {
@@ -42,10 +43,6 @@ struct GStep {
 };
 static_assert(sizeof(GStep<float>) == 48 && sizeof(GStep<double>) == 80, "GStep layout is shared with geometry_plan.step_dtype");
 
-__device__ __forceinline__ float sqrt_(float v) { return sqrtf(v); }
-__device__ __forceinline__ double sqrt_(double v) { return sqrt(v); }
-__device__ __forceinline__ float exp_(float v) { return expf(v); }
-__device__ __forceinline__ double exp_(double v) { return exp(v); }
 template <typename T> __device__ __forceinline__ T min_(T a, T b) { return a < b ? a : b; }
 template <typename T> __device__ __forceinline__ T max_(T a, T b) { return a > b ? a : b; }
 
@@ -313,13 +310,6 @@ __global__ __launch_bounds__(kThreads) void xy_grid_kernel(int64_t ny, int64_t n
         if (i < ny) y[i] = T(i - ny / 2) * dx;
     }
 }
-
-__device__ __forceinline__ float hypot_(float a, float b) { return hypotf(a, b); }
-__device__ __forceinline__ double hypot_(double a, double b) { return hypot(a, b); }
-__device__ __forceinline__ float atan2_(float a, float b) { return atan2f(a, b); }
-__device__ __forceinline__ double atan2_(double a, double b) { return atan2(a, b); }
-__device__ __forceinline__ void sincos_(float t, float* s, float* c) { sincosf(t, s, c); }
-__device__ __forceinline__ void sincos_(double t, double* s, double* c) { sincos(t, s, c); }
 
 // separable: x has nx values and y ny values, the outputs ny x nx; else all four hold ny x nx values
 template <typename T>

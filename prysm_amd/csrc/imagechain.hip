@@ -10,8 +10,8 @@
 //    integer of the bin times 1 / (n dx) in double, rounded once to the working precision -- or from vectors or arrays.
 //  - pm_polar_resample: the bilinear gather of uniform_cart_to_polar.
 //  - pm_centroid: sum d, sum row d, sum col d in double; pm_psf_size: the maximum of a polar map, the threshold crossing of each
-//    row (one wavefront per row) and their mean.  Partials per workgroup in a workspace, folded in a fixed order by a second launch:
-//    no atomics, the same bits every run, nothing read on the host.
+//    row (one wavefront per row) and their mean.  Partials per workgroup in a workspace, folded in a fixed order by a second launch
+//    (both stages: pm_reduce.h): no atomics, the same bits every run, nothing read on the host.
 //
 // The pointwise kernels ride on pm_sweep.h.  The unit is compiled with -ffp-contract=off (csrc/Makefile): every product and sum is
 // rounded by itself, in the order written, which prysm_amd/imagechain_plan.py restates in numpy.  J1 is the Chebyshev series of
@@ -20,29 +20,12 @@
 
 #include "fibers_coefs.h"
 #include "pm_entry.h"
+#include "pm_math.h"
+#include "pm_reduce.h"
 #include "pm_sweep.h"
 
 namespace pm {
 namespace {
-
-__device__ __forceinline__ float sqrt_(float v) { return sqrtf(v); }
-__device__ __forceinline__ double sqrt_(double v) { return sqrt(v); }
-__device__ __forceinline__ float exp_(float v) { return expf(v); }
-__device__ __forceinline__ double exp_(double v) { return exp(v); }
-__device__ __forceinline__ float sin_(float v) { return sinf(v); }
-__device__ __forceinline__ double sin_(double v) { return sin(v); }
-__device__ __forceinline__ float cos_(float v) { return cosf(v); }
-__device__ __forceinline__ double cos_(double v) { return cos(v); }
-__device__ __forceinline__ float acos_(float v) { return acosf(v); }
-__device__ __forceinline__ double acos_(double v) { return acos(v); }
-__device__ __forceinline__ float abs_(float v) { return fabsf(v); }
-__device__ __forceinline__ double abs_(double v) { return fabs(v); }
-__device__ __forceinline__ float hypot_(float a, float b) { return hypotf(a, b); }
-__device__ __forceinline__ double hypot_(double a, double b) { return hypot(a, b); }
-__device__ __forceinline__ float atan2_(float a, float b) { return atan2f(a, b); }
-__device__ __forceinline__ double atan2_(double a, double b) { return atan2(a, b); }
-__device__ __forceinline__ void sincos_(float t, float* s, float* c) { sincosf(t, s, c); }
-__device__ __forceinline__ void sincos_(double t, double* s, double* c) { sincos(t, s, c); }
 
 constexpr double kPi = 3.141592653589793;
 
@@ -341,34 +324,15 @@ constexpr int kRedWgs = 1024;        // most workgroups of a reduction pass: as 
 constexpr int kCrossWaves = kRedThreads / 64;
 constexpr int kCrossWgs = 1024;      // most workgroups of the crossing pass, kCrossWaves rows each per trip
 
-int red_groups(int64_t n) { return int(std::min<int64_t>(kRedWgs, (n + kRedThreads - 1) / kRedThreads)); }
-int cross_groups(int64_t rows) { return int(std::min<int64_t>(kCrossWgs, (rows + kCrossWaves - 1) / kCrossWaves)); }
-
-// the workgroup's combination of a[k] over its threads to dst[k]: LDS tree, the same order every run (csrc/optym.hip wg_fold)
-template <int NS, bool MAX>
-__device__ __forceinline__ void wg_fold(const double (&a)[NS], double* __restrict__ dst) {
-    __shared__ double red[NS][kRedThreads];
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < NS; ++k) red[k][tid] = a[k];
-    __syncthreads();
-    for (int s = kRedThreads / 2; s > 0; s >>= 1) {
-        if (tid < s)
-#pragma unroll
-            for (int k = 0; k < NS; ++k) {
-                const double u = red[k][tid], w = red[k][tid + s];
-                red[k][tid] = MAX ? (w > u ? w : u) : u + w;
-            }
-        __syncthreads();
-    }
-    if (tid < NS) dst[tid] = red[tid][0];
-}
+int red_groups(int64_t n) { return reduce_groups(n, kRedThreads, kRedWgs); }
+int cross_groups(int64_t rows) { return reduce_groups(rows, kCrossWaves, kCrossWgs); }
 
 // pass A over an m x n array (rows ld apart): MAX: the maximum; else sum d, sum row d, sum col d.  partial[wg * NS + k]
 template <typename T, bool MAX>
 __global__ __launch_bounds__(kRedThreads) void reduce_kernel(int64_t m, int64_t n, const T* __restrict__ d, int64_t ld,
                                                              double* __restrict__ partial) {
     constexpr int NS = MAX ? 1 : 3;
+    using Op = std::conditional_t<MAX, FoldMax, FoldSum>;
     double a[NS];
     a[0] = MAX ? -INFINITY : 0.0;
     if constexpr (!MAX) a[1] = a[2] = 0.0;
@@ -384,18 +348,13 @@ __global__ __launch_bounds__(kRedThreads) void reduce_kernel(int64_t m, int64_t 
             a[2] = a[2] + double(c) * v;
         }
     }
-    wg_fold<NS, MAX>(a, partial + int64_t(blockIdx.x) * NS);
+    wg_fold<kRedThreads, Op>(threadIdx.x, a, partial + int64_t(blockIdx.x) * NS);
 }
 
 // pass B, one workgroup: the partials in a fixed order.  Centroid: out = (sum row d / sum d, sum col d / sum d).
 __global__ __launch_bounds__(kRedThreads) void centroid_fold_kernel(int nparts, const double* __restrict__ partial, double* __restrict__ out) {
-    __shared__ double tot[3];
-    double a[3] = {0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < nparts; i += kRedThreads)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) a[k] = a[k] + partial[int64_t(i) * 3 + k];
-    wg_fold<3, false>(a, tot);
-    __syncthreads();
+    double tot[3];
+    fold_partials<kRedThreads, FoldSum>(threadIdx.x, nparts, partial, 0.0, tot);
     if (threadIdx.x == 0) {
         out[0] = tot[1] / tot[0];
         out[1] = tot[2] / tot[0];
@@ -406,11 +365,8 @@ __global__ __launch_bounds__(kRedThreads) void centroid_fold_kernel(int nparts, 
 template <typename T>
 __global__ __launch_bounds__(kRedThreads) void threshold_fold_kernel(int nparts, const double* __restrict__ partial, int relative, double value,
                                                                      double* __restrict__ sc) {
-    __shared__ double tot[1];
-    double a[1] = {-INFINITY};
-    for (int i = threadIdx.x; i < nparts; i += kRedThreads) a[0] = partial[i] > a[0] ? partial[i] : a[0];
-    wg_fold<1, true>(a, tot);
-    __syncthreads();
+    double tot[1];
+    fold_partials<kRedThreads, FoldMax>(threadIdx.x, nparts, partial, -INFINITY, tot);
     if (threadIdx.x == 0) sc[0] = relative ? double(T(value) * T(tot[0])) : double(T(value));
 }
 
@@ -461,14 +417,12 @@ __global__ __launch_bounds__(kRedThreads) void crossing_kernel(int64_t rows, int
 // one workgroup: out = (mean of the crossings, their count); a mean of 0 when there is none
 __global__ __launch_bounds__(kRedThreads) void crossing_mean_kernel(int64_t rows, const double* __restrict__ cross, const double* __restrict__ has,
                                                                     double* __restrict__ out) {
-    __shared__ double tot[2];
-    double a[2] = {0.0, 0.0};
+    double a[2] = {0.0, 0.0}, tot[2];
     for (int64_t i = threadIdx.x; i < rows; i += kRedThreads) {
         a[0] = a[0] + cross[i];
         a[1] = a[1] + has[i];
     }
-    wg_fold<2, false>(a, tot);
-    __syncthreads();
+    wg_total<kRedThreads, FoldSum>(threadIdx.x, a, tot);
     if (threadIdx.x == 0) {
         out[0] = tot[1] > 0.0 ? tot[0] / tot[1] : 0.0;
         out[1] = tot[1];

@@ -6,6 +6,7 @@
 #include <initializer_list>
 
 #include "pm_entry.h"
+#include "pm_math.h"
 
 namespace pm {
 namespace {
@@ -21,9 +22,6 @@ struct Runs {
     using vec = T __attribute__((ext_vector_type(W)));
     static __device__ __forceinline__ int64_t at(int64_t base, int lane, int q) { return base + (q / W) * 64 * W + lane * W + q % W; }
 };
-
-__device__ __forceinline__ void sincos_(float t, float* s, float* c) { sincosf(t, s, c); }
-__device__ __forceinline__ void sincos_(double t, double* s, double* c) { sincos(t, s, c); }
 
 template <typename T>
 __device__ __forceinline__ T wave_sum(T s) {

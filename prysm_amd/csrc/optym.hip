@@ -3,9 +3,10 @@
 //  - pm_optym_cost: mean_square_error, bias_and_gain_invariant_error and negative_loglikelihood with their gradients.  A mask is a
 //    per-element predicate (bytes), never a compaction: the selected count is one of the sums, so nothing is read on the host.
 //      pass A: one read of M, D and the mask; every thread keeps the sums the cost needs in DOUBLE (the element arithmetic is double
-//        too: the kernels are memory-bound), a workgroup of 256 folds them in LDS in a fixed order and leaves one partial per sum in
-//        the workspace.  At most kCostWgs workgroups, grid-stride.
-//      fold: ONE workgroup adds the partials in a fixed order and forms the scalars (1/N, alpha, beta, R) in double on the device.
+//        too: the kernels are memory-bound), a workgroup of 256 folds them in LDS in a fixed order (pm_reduce.h wg_fold) and leaves
+//        one partial per sum in the workspace.  At most kCostWgs workgroups, grid-stride.
+//      fold: ONE workgroup adds the partials in a fixed order (pm_reduce.h fold_partials) and forms the scalars (1/N, alpha, beta, R)
+//        in double on the device.
 //      pass B: the gradient store (zero where the mask is false).  For the bias-and-gain-invariant cost it also carries the partials
 //        of sum(raw_err^2) and a second fold forms R * that sum, so the cost is the reference's sum of squared residuals.
 //    No float atomics, no tickets: the same launch shape adds the same numbers in the same order, run after run.
@@ -28,6 +29,7 @@
 #include <cmath>
 
 #include "pm_entry.h"
+#include "pm_reduce.h"
 #include "pm_sweep.h"
 
 namespace pm {
@@ -44,23 +46,6 @@ constexpr int kSoftThreads = 256;
 constexpr size_t kWsDoubles = size_t(kScalars) + size_t(kCostWgs) * kCostSums + size_t(kCostWgs);
 
 __host__ __device__ constexpr int sums_of(int kind) { return kind == PM_COST_BGI ? 6 : 2; }
-
-// the workgroup's sum of a[k] over its threads to partial[wg * NS + k]: LDS tree, the same order every run
-template <int NS>
-__device__ __forceinline__ void wg_fold(const double (&a)[NS], double* __restrict__ dst) {
-    __shared__ double red[NS][kCostThreads];
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < NS; ++k) red[k][tid] = a[k];
-    __syncthreads();
-    for (int s = kCostThreads / 2; s > 0; s >>= 1) {
-        if (tid < s)
-#pragma unroll
-            for (int k = 0; k < NS; ++k) red[k][tid] = red[k][tid] + red[k][tid + s];
-        __syncthreads();
-    }
-    if (tid < NS) dst[tid] = red[tid][0];
-}
 
 template <typename T, int KIND>
 __global__ __launch_bounds__(kCostThreads) void cost_sums_kernel(int64_t n, const T* __restrict__ M, const T* __restrict__ D, double dscalar,
@@ -87,23 +72,7 @@ __global__ __launch_bounds__(kCostThreads) void cost_sums_kernel(int64_t n, cons
             a[5] = a[5] + d * d;
         }
     }
-    wg_fold<NS>(a, partial + int64_t(blockIdx.x) * NS);
-}
-
-// one workgroup: sum k of the `nparts` partials (stride NS) in a fixed order
-template <int NS>
-__device__ __forceinline__ void fold_partials(int nparts, const double* __restrict__ partial, double (&total)[NS]) {
-    __shared__ double out[NS];
-    double a[NS];
-#pragma unroll
-    for (int k = 0; k < NS; ++k) a[k] = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += kCostThreads)
-#pragma unroll
-        for (int k = 0; k < NS; ++k) a[k] = a[k] + partial[int64_t(i) * NS + k];
-    wg_fold<NS>(a, out);
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NS; ++k) total[k] = out[k];
+    wg_fold<kCostThreads, FoldSum>(threadIdx.x, a, partial + int64_t(blockIdx.x) * NS);
 }
 
 template <typename T, int KIND>
@@ -111,7 +80,7 @@ __global__ __launch_bounds__(kCostThreads) void cost_fold_kernel(int nparts, con
                                                                   T* __restrict__ cost) {
     constexpr int NS = sums_of(KIND);
     double s[NS];
-    fold_partials<NS>(nparts, partial, s);
+    fold_partials<kCostThreads, FoldSum>(threadIdx.x, nparts, partial, 0.0, s);
     if (threadIdx.x != 0) return;
     const double N = s[0];
     sc[0] = N;
@@ -157,20 +126,20 @@ __global__ __launch_bounds__(kCostThreads) void cost_grad_kernel(int64_t n, cons
             grad[i] = T(2.0 * c1 * alpha * raw);
         }
     }
-    if constexpr (KIND == PM_COST_BGI) wg_fold<1>(a, partial + blockIdx.x);
+    if constexpr (KIND == PM_COST_BGI) wg_fold<kCostThreads, FoldSum>(threadIdx.x, a, partial + blockIdx.x);
 }
 
 template <typename T>
 __global__ __launch_bounds__(kCostThreads) void cost_fold2_kernel(int nparts, const double* __restrict__ partial, const double* __restrict__ sc,
                                                                    T* __restrict__ cost) {
     double s[1];
-    fold_partials<1>(nparts, partial, s);
+    fold_partials<kCostThreads, FoldSum>(threadIdx.x, nparts, partial, 0.0, s);
     if (threadIdx.x == 0) *cost = T(sc[1] * s[0]);
 }
 
 template <typename T, int KIND>
 int cost_run(int64_t n, const void* M, const void* D, double dscalar, const void* mask, void* cost, void* grad, double* ws, hipStream_t st) {
-    const int wgs = int(std::min<int64_t>(kCostWgs, (n + kCostThreads - 1) / kCostThreads));
+    const int wgs = reduce_groups(n, kCostThreads, kCostWgs);
     double* sc = ws;
     double* pa = ws + kScalars;
     double* pb = pa + size_t(kCostWgs) * kCostSums;

@@ -17,13 +17,14 @@
 //    above (kept in the workspace, [boundary][sample]) and a_0 = [Bbar, Cbar]^T, a_{j+1} = M_j^H a_j a scan from the ambient side.  No
 //    matrix is stored or inverted.  A thread's contribution to layer j is summed over its wavefront in DOUBLE with cross-lane shuffles
 //    (a fixed butterfly), one partial per wavefront and layer goes to the workspace, and a second launch adds the partials of a layer
-//    in a fixed order: no atomics, the same bits run after run.
+//    in a fixed order (pm_reduce.h fold_partials): no atomics, the same bits run after run.
 //
 // prysm_amd/thinfilm_plan.py is this file in numpy.  The unit is compiled with -ffp-contract=off (csrc/Makefile) so that every product
 // and sum is rounded by itself, as numpy does; sincos, sqrt, hypot and expm1 are the accurate library functions.
 #include <cmath>
 
 #include "pm_entry.h"
+#include "pm_reduce.h"
 
 namespace pm {
 namespace {
@@ -300,18 +301,9 @@ __global__ __launch_bounds__(kThreads) void grad_kernel(Operands<T> op, int64_t 
 // one workgroup per layer: its partials in a fixed order
 template <typename T>
 __global__ __launch_bounds__(kThreads) void grad_fold_kernel(int64_t nparts, const double* __restrict__ partial, int accumulate, T* __restrict__ grad) {
-    __shared__ double red[kThreads];
-    const int tid = threadIdx.x;
-    const double* row = partial + int64_t(blockIdx.x) * nparts;
-    double a = 0.0;
-    for (int64_t i = tid; i < nparts; i += kThreads) a = a + row[i];
-    red[tid] = a;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] + red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) grad[blockIdx.x] = accumulate ? grad[blockIdx.x] + T(red[0]) : T(red[0]);
+    double sum[1];
+    fold_partials<kThreads, FoldSum>(threadIdx.x, nparts, partial + int64_t(blockIdx.x) * nparts, 0.0, sum);
+    if (threadIdx.x == 0) grad[blockIdx.x] = accumulate ? grad[blockIdx.x] + T(sum[0]) : T(sum[0]);
 }
 
 bool pol_ok(int32_t pol) { return pol == PM_TF_S || pol == PM_TF_P || pol == PM_TF_BOTH; }

@@ -172,6 +172,42 @@ def test_white_balance_of_views_and_stacks(bayer, g):
     assert np.array_equal(tonp(got), want)
 
 
+def _class_maxima(bayer, t):
+    """pm_bayer_class_max of one contiguous mosaic, called as bayer._scale calls it; class 2 * (r & 1) + (c & 1)"""
+    from prysm_amd import _lib as L
+    lib = L.load()
+    v, ld, bs = bayer._mosaic_view(t, 'mosaic')
+    B, m, n = v.shape
+    maxima = torch.empty(4, dtype=torch.float64, device=t.device)
+    ws = L.workspace(int(lib.pm_bayer_class_max_workspace()))
+    L.check(lib.pm_bayer_class_max(bayer._code(t.dtype), L.PM_BAYER_MOSAIC, B, m, n, L.ptr(v), ld, bs, L.ptr(maxima), L.ptr(ws), ws.numel(), L.stream_ptr()))
+    return tonp(maxima)
+
+
+@pytest.mark.parametrize('dtype', ['float64', 'float32'])
+def test_class_maxima_where_the_second_stage_loops_and_ends_ragged(bayer, dtype):
+    """362 x 130: the first stage runs 3 x 91 workgroups (64 columns by 4 rows each, at most kMaxPartials = 4096 of them), so the
+    second stage folds 273 partials: more than its 256 threads and no multiple of them.  The last workgroup, and the last partial,
+    holds rows 360, 361 of columns 128, 129: one sample of each class.  The maxima are put there, so a second stage that stops at
+    256 partials or drops the ragged end misses all four.  Comparisons only: the result equals numpy's, NaN included."""
+    m, n = 362, 130
+    assert ((n + 63) // 64, min((m + 3) // 4, 4096 // ((n + 63) // 64))) == (3, 91)
+    src = np.random.default_rng(273).random((m, n)).astype(dtype)
+    src[360:, 128:] = np.array([[2.5, 3.5], [4.5, 5.5]], dtype=dtype)
+    want = np.array([src[i::2, j::2].max() for i in (0, 1) for j in (0, 1)], dtype=np.float64)
+    assert list(want) == [2.5, 3.5, 4.5, 5.5]
+    got = _class_maxima(bayer, dev(src))
+    print(dtype, 'maxima', got)
+    assert np.array_equal(got, want)
+    # a NaN in one class, seen by the last workgroup only: that class is NaN (numpy's max), the other three are unchanged
+    src[361, 128] = np.nan
+    want_nan = np.array([src[i::2, j::2].max() for i in (0, 1) for j in (0, 1)], dtype=np.float64)
+    assert np.isnan(want_nan[2]) and np.array_equal(np.delete(want_nan, 2), np.delete(want, 2))
+    got = _class_maxima(bayer, dev(src))
+    print(dtype, 'maxima with a NaN', got)
+    assert np.array_equal(got, want_nan, equal_nan=True)
+
+
 def test_assemble_superresolved_against_the_fixture(bayer, g):
     """rel_max against the reference.  Observed for the reference-vs-model pair (the same transforms in numpy with the separable
     multiplier): 5.7e-16 and 5.1e-16 in float64; the same cases computed in float32: 1.7e-7 and 1.5e-7, the floor of that precision.

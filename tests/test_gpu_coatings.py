@@ -211,6 +211,30 @@ def test_gradient_repeats_bitwise_and_accumulates(pa, dt):
     assert torch.equal(both, gs + gp)
 
 
+@pytest.mark.parametrize('dt', DTYPES)
+def test_gradient_fold_past_256_partials_places_every_partial(pa, dt):
+    """K = 64 * 257 + 1 samples give 258 partials per layer, so the folding workgroup's threads 0 and 1 make a second trip and the last
+    partial comes from a wavefront with one live lane.  With dR one-hot at sample k every other partial is an exact zero, and a sum
+    of one value and zeros is that value in any order: the gradient must be, bit for bit, the gradient of sample k alone with
+    dR = 1.  k = 0: the first partial; k = 64 * 256: the first partial of the second trip; k = K - 1: the ragged last wavefront.  A
+    dropped, doubled or misplaced partial shows as a mismatch."""
+    from prysm_amd import _ops
+    K, Ly = 64 * 257 + 1, 2
+    assert -(-K // 64) == 258      # parts_of(K) of csrc/thinfilm.hip: one partial per wavefront
+    flat = _random_operands(np.random.default_rng(258), K, Ly, True)
+    cd = torch.complex128 if np.dtype(dt) == np.complex128 else torch.complex64
+    op = _ops.TfOperands(cd, K, flat['wvl'], flat['theta'], flat['indices'], flat['thicknesses'], flat['nsub'], flat['n0'])
+    for k in (0, 64 * 256, K - 1):
+        dR = np.zeros(K)
+        dR[k] = 1.0
+        got = _ops.tf_thickness_grad(op, 's', dR, None)
+        one = _ops.TfOperands(cd, 1, flat['wvl'][k:k + 1], flat['theta'][k:k + 1], flat['indices'][:, k:k + 1], flat['thicknesses'][:, k:k + 1],
+                              flat['nsub'][k:k + 1], flat['n0'])
+        want = _ops.tf_thickness_grad(one, 's', np.ones(1), None)
+        print(f'k={k} {np.dtype(dt).name}: fold {tonp(got)}, sample alone {tonp(want)}')
+        assert float(want.abs().min()) > 0 and torch.equal(got, want), (k, tonp(got), tonp(want))
+
+
 def _refinement(C, O, term=None):
     n6, W, A, nsub = CC.traj_operands()
     term = C.Reflectance(W, A, 'avg', 0.0, 1.0) if term is None else term
