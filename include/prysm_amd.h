@@ -923,7 +923,8 @@ int pm_mdft_basis_grid(int32_t dtype, int64_t M, int64_t N, double f_step, doubl
  *   opA: 0 = A, 1 = conj(A), 2 = A^T, 3 = A^H     (A stored M x K for 0/1, K x M for 2/3)
  *   opB: likewise                                   (B stored K x N for 0/1, N x K for 2/3)
  * The two GEMMs of fttools.MDFT.__call__ / .adjoint (prysm/fttools.py:201-228).
- * Leading dimensions must be below 2^22 elements (PM_ERR_UNSUPPORTED otherwise). */
+ * Leading dimensions must be below 2^22 elements (PM_ERR_UNSUPPORTED otherwise) and, for an operand or a result of more than one
+ * stored row, not below the stored row (PM_ERR_ARG; pm_cgemm_abs2 likewise, after its PM_ERR_UNSUPPORTED). */
 int pm_cgemm(int32_t dtype, int32_t opA, int32_t opB, int64_t M, int64_t N, int64_t K, double alpha,
              const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, void* workspace,
              size_t workspace_bytes, void* stream);

@@ -740,9 +740,23 @@ def mdft_basis_grid(M, N, f_step, f_shift, f_scale, x_step, sign, cdtype):
     return E
 
 
+def _gemm_operands(name, A, B):
+    """what the library cannot see behind two pointers: both operands 2-D, of one complex dtype, on one device, rows contiguous"""
+    for which, t in (('A', A), ('B', B)):
+        if t.dim() != 2:
+            raise ValueError(f'{name}: {which} must be 2-D, got {t.dim()} dimensions')
+        if t.shape[1] > 1 and t.stride(1) != 1:     # the stride of an axis of one element means nothing
+            raise ValueError(f'{name}: {which} must have a unit inner stride, got {t.stride(1)} (pass the transposed storage and op 2 / 3)')
+    if A.dtype != B.dtype:
+        raise ValueError(f'{name}: A and B must have the same dtype, got {A.dtype} and {B.dtype}')
+    if A.device != B.device:
+        raise ValueError(f'{name}: A and B must be on the same device, got {A.device} and {B.device}')
+
+
 def cgemm(A, B, opA=0, opB=0, alpha=1.0):
     """alpha * op(A) @ op(B) on the MFMA cores.  op: 0 none, 1 conj, 2 transpose, 3 conjugate transpose."""
     lib = L.load()
+    _gemm_operands('cgemm', A, B)
     M, K = (A.shape[1], A.shape[0]) if opA & 2 else A.shape
     K2, N = (B.shape[1], B.shape[0]) if opB & 2 else B.shape
     if K != K2:
@@ -760,6 +774,7 @@ def cgemm_abs2(A, B, opA=0, opB=0, alpha=1.0, out=None, weight=1.0):
     accumulate in the product's epilogue, no complex result in memory).  Returns None when the shapes are not the LDS-DMA
     kernel's (the caller composes cgemm + abs2)."""
     lib = L.load()
+    _gemm_operands('cgemm_abs2', A, B)
     M, K = (A.shape[1], A.shape[0]) if opA & 2 else A.shape
     K2, N = (B.shape[1], B.shape[0]) if opB & 2 else B.shape
     if K != K2:

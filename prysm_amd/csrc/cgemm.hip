@@ -767,6 +767,17 @@ int cgemm_ws(int opA, int opB, int64_t M, int64_t N, int64_t K, double alpha, co
     return cgemm_ws_staged<T, 8>(opA, opB, M, N, K, alpha, A, lda, B, ldb, C, ldc, ws, ws_bytes, st);
 }
 
+// the leading dimension that is shorter than its stored row, if any (nullptr: none).  A is stored M x K (op 0 / 1) or K x M (op 2 / 3),
+// B K x N or N x K, the result M x N; an operand of one stored row never uses its leading dimension
+static const char* gemm_short_ld(int opA, int opB, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                                 const char* out_name) {
+    const bool at = (opA & 2) != 0, bt = (opB & 2) != 0;
+    if ((at ? K : M) > 1 && lda < (at ? M : K)) return "lda";
+    if ((bt ? N : K) > 1 && ldb < (bt ? K : N)) return "ldb";
+    if (M > 1 && ldc < N) return out_name;
+    return nullptr;
+}
+
 }  // namespace pm
 
 using namespace pm;
@@ -785,14 +796,15 @@ int pm_cgemm(int32_t dtype, int32_t opA, int32_t opB, int64_t M, int64_t N, int6
     if (M == 0 || N == 0) return 0;
     if (lda >= (int64_t(1) << 22) || ldb >= (int64_t(1) << 22))   // per-thread 32-bit byte offsets inside a K-tile
         return fail(PM_ERR_UNSUPPORTED, "pm_cgemm: leading dimensions of 2^22 elements or more are not supported");
+    if (dtype != PM_C64 && dtype != PM_C128) return fail(PM_ERR_ARG, "pm_cgemm: dtype must be PM_C64 or PM_C128");
+    if (const char* which = gemm_short_ld(opA, opB, M, N, K, lda, ldb, ldc, "ldc"))
+        return fail(PM_ERR_ARG, "pm_cgemm: %s is smaller than the stored row", which);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (dtype == PM_C64)
         return cgemm_ws<float>(opA, opB, M, N, K, alpha, (const cx<float>*)A, lda, (const cx<float>*)B, ldb, (cx<float>*)C, ldc,
                                workspace, workspace_bytes, st);
-    if (dtype == PM_C128)
-        return cgemm_ws<double>(opA, opB, M, N, K, alpha, (const cx<double>*)A, lda, (const cx<double>*)B, ldb, (cx<double>*)C,
-                                ldc, workspace, workspace_bytes, st);
-    return fail(PM_ERR_ARG, "pm_cgemm: dtype must be PM_C64 or PM_C128");
+    return cgemm_ws<double>(opA, opB, M, N, K, alpha, (const cx<double>*)A, lda, (const cx<double>*)B, ldb, (cx<double>*)C, ldc,
+                            workspace, workspace_bytes, st);
 }
 
 int pm_cgemm_abs2(int32_t dtype, int32_t opA, int32_t opB, int64_t M, int64_t N, int64_t K, double alpha, const void* A,
@@ -807,9 +819,12 @@ int pm_cgemm_abs2(int32_t dtype, int32_t opA, int32_t opB, int64_t M, int64_t N,
     const cx<float>* a = reinterpret_cast<const cx<float>*>(A);
     const cx<float>* b = reinterpret_cast<const cx<float>*>(B);
     if (dtype == PM_C64 && lda < (int64_t(1) << 22) && ldb < (int64_t(1) << 22) && gemm_dma_plan(M, N, K, &dp) && (lda % 2) == 0 &&
-        (ldb % 2) == 0 && reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(B) % 16 == 0)
+        (ldb % 2) == 0 && reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(B) % 16 == 0) {
+        if (const char* which = gemm_short_ld(opA, opB, M, N, K, lda, ldb, ldr, "ldr"))
+            return fail(PM_ERR_ARG, "pm_cgemm_abs2: %s is smaller than the stored row", which);
         return cgemm_dma_run(opA, opB, M, N, K, alpha, a, lda, b, ldb, reinterpret_cast<cx<float>*>(R), ldr, workspace, workspace_bytes, st, dp,
                              DmaEpi{1, float(weight), accumulate ? 1 : 0});
+    }
     return fail(PM_ERR_UNSUPPORTED, "pm_cgemm_abs2: only the LDS-DMA shapes (complex64, multiples of 64 x 64 x 16, aligned operands); "
                                     "compose pm_cgemm and pm_abs2");
 }

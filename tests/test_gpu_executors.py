@@ -4,6 +4,10 @@ against each other and the oracle, executors built from grid parameters (csrc/cg
 All through the C ABI (ctypes -> libprysm_amd.so), against the fp64 oracle / numpy first and a second HIP route only afterwards.
 Tolerances (max error / max magnitude against fp64): 1e-10 complex128, 5e-6 complex64 transforms, 3e-5 the MFMA matrix DFT.
 (Regrouped in round 6 from the per-round files of rounds 2 - 5; the tests themselves are unchanged.)
+
+The two direct GEMM tests here run large complex64 multiples of 64 x 64 x 16 on contiguous operands, i.e. the LDS-DMA kernel at its
+production shapes, against a max-error tolerance.  tests/test_gpu_cgemm.py is the kernel-level file: every kernel form, edge, operand
+layout and leading dimension of csrc/cgemm.hip on exact integer data compared element for element.
 """
 import ctypes
 import json
