@@ -19,6 +19,11 @@ namespace {
 constexpr int kLatticeBlockX = 64, kLatticeBlockY = 4;
 constexpr int kFirTX = 32, kFirTY = 16, kFirThreads = 256;
 constexpr int kMaxGridZ = 65535;
+constexpr int kMaxGridY = 65535;        // as csrc/pm_sweep.h: at most 65535 workgroups down the rows, more rows by the grid-stride step
+
+// the rows of a thread of a (x, y) block: its own, then every gridDim.y * blockDim.y-th after it
+__device__ __forceinline__ int64_t row_first() { return int64_t(blockIdx.y) * blockDim.y + threadIdx.y; }
+__device__ __forceinline__ int64_t row_step() { return int64_t(gridDim.y) * blockDim.y; }
 
 template <typename T> struct FirK;
 template <> struct FirK<float> { static constexpr int K = 14; };
@@ -45,13 +50,17 @@ __global__ void lattice_scatter_kernel(int64_t batch, int rows, int cols, int na
                                        T scale, const T* __restrict__ in, int64_t in_ld, int64_t in_bstride, T* __restrict__ out,
                                        int64_t out_ld, int64_t out_bstride) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    const int r = blockIdx.y * blockDim.y + threadIdx.y;
-    if (c >= cols || r >= rows) return;
-    const int dy = r - y0, dx = c - x0;
-    const int i = dy / sy, j = dx / sx;
-    const bool hit = dy >= 0 && dx >= 0 && dy == i * sy && dx == j * sx && i < nact_y && j < nact_x;
-    for (int64_t b = blockIdx.z; b < batch; b += gridDim.z)
-        out[b * out_bstride + r * out_ld + c] = hit ? scale * in[b * in_bstride + i * in_ld + j] : T(0);
+    if (c >= cols) return;
+    const int dx = c - x0;
+    const int j = dx / sx;
+    const bool hit_x = dx >= 0 && dx == j * sx && j < nact_x;
+    for (int64_t r = row_first(); r < rows; r += row_step()) {
+        const int dy = int(r) - y0;
+        const int i = dy / sy;
+        const bool hit = hit_x && dy >= 0 && dy == i * sy && i < nact_y;
+        for (int64_t b = blockIdx.z; b < batch; b += gridDim.z)
+            out[b * out_bstride + r * out_ld + c] = hit ? scale * in[b * in_bstride + i * in_ld + j] : T(0);
+    }
 }
 
 template <typename T, bool IS_CX>
@@ -59,10 +68,10 @@ __global__ void lattice_gather_kernel(int64_t batch, int nact_y, int nact_x, int
                                       const T* __restrict__ in, int64_t in_ld, int64_t in_bstride, T* __restrict__ out, int64_t out_ld,
                                       int64_t out_bstride) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y * blockDim.y + threadIdx.y;
-    if (j >= nact_x || i >= nact_y) return;
-    for (int64_t b = blockIdx.z; b < batch; b += gridDim.z)
-        out[b * out_bstride + i * out_ld + j] = scale * load_re<T, IS_CX>(in, b * in_bstride + int64_t(y0 + i * sy) * in_ld + (x0 + j * sx));
+    if (j >= nact_x) return;
+    for (int64_t i = row_first(); i < nact_y; i += row_step())
+        for (int64_t b = blockIdx.z; b < batch; b += gridDim.z)
+            out[b * out_bstride + i * out_ld + j] = scale * load_re<T, IS_CX>(in, b * in_bstride + (y0 + i * sy) * in_ld + (x0 + j * sx));
 }
 
 // ---------------------------------------------------------------- warp: prefilter
@@ -77,8 +86,10 @@ __global__ __launch_bounds__(kFirThreads) void spline_fir_kernel(int64_t batch, 
     constexpr int NV = (HH * kFirTX + kFirThreads - 1) / kFirThreads;
     __shared__ T s[HH * HW];
     const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * kFirTX, y0 = blockIdx.y * kFirTY;
+    const int x0 = blockIdx.x * kFirTX;
     const T sqrt3 = T(1.7320508075688772), z = T(-0.2679491924311228);
+    // tile rows past kMaxGridY * kFirTY rows are this workgroup's next trips (rows <= INT32_MAX / 2, so y0 + the step stays an int)
+    for (int y0 = blockIdx.y * kFirTY; y0 < rows; y0 += gridDim.y * kFirTY)
     for (int64_t b = blockIdx.z; b < batch; b += gridDim.z) {
         for (int e = tid; e < HH * HW; e += kFirThreads) {
             const int hr = e / HW, hc = e - hr * HW;
@@ -150,47 +161,49 @@ template <typename T>
 __global__ void spline_sample_kernel(int64_t batch, int rows, int cols, const T* __restrict__ coeff, Homography H, double scale, int out_rows,
                                      int out_cols, int off_y, int off_x, T* __restrict__ out, int64_t out_ld, int64_t out_bstride) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    const int r = blockIdx.y * blockDim.y + threadIdx.y;
-    if (c >= out_cols || r >= out_rows) return;
-    const int R = r + off_y, C = c + off_x;
-    bool inside = R >= 0 && R < rows && C >= 0 && C < cols;
-    int iy[4], ix[4];
-    double wy[4], wx[4];
-    if (inside) {
-        // apply_homography (prysm/coordinates.py:545-570): (x', y', w) = H (C, R, 1), then x'/w, y'/w -- all fp64
-        const double xc = double(C), yr = double(R);
-        const double xp = H.m[0] * xc + H.m[1] * yr + H.m[2];
-        const double yp = H.m[3] * xc + H.m[4] * yr + H.m[5];
-        const double w = H.m[6] * xc + H.m[7] * yr + H.m[8];
-        const double x = xp / w, y = yp / w;
-        inside = x >= 0.0 && x <= double(cols - 1) && y >= 0.0 && y <= double(rows - 1);
+    if (c >= out_cols) return;
+    for (int64_t r64 = row_first(); r64 < out_rows; r64 += row_step()) {
+        const int r = int(r64);
+        const int R = r + off_y, C = c + off_x;
+        bool inside = R >= 0 && R < rows && C >= 0 && C < cols;
+        int iy[4], ix[4];
+        double wy[4], wx[4];
         if (inside) {
-            const double fy = floor(y), fx = floor(x);
-            bspline3_weights(y - fy, wy);
-            bspline3_weights(x - fx, wx);
+            // apply_homography (prysm/coordinates.py:545-570): (x', y', w) = H (C, R, 1), then x'/w, y'/w -- all fp64
+            const double xc = double(C), yr = double(R);
+            const double xp = H.m[0] * xc + H.m[1] * yr + H.m[2];
+            const double yp = H.m[3] * xc + H.m[4] * yr + H.m[5];
+            const double w = H.m[6] * xc + H.m[7] * yr + H.m[8];
+            const double x = xp / w, y = yp / w;
+            inside = x >= 0.0 && x <= double(cols - 1) && y >= 0.0 && y <= double(rows - 1);
+            if (inside) {
+                const double fy = floor(y), fx = floor(x);
+                bspline3_weights(y - fy, wy);
+                bspline3_weights(x - fx, wx);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                iy[k] = mirror_index(int(fy) - 1 + k, rows);
-                ix[k] = mirror_index(int(fx) - 1 + k, cols);
+                for (int k = 0; k < 4; ++k) {
+                    iy[k] = mirror_index(int(fy) - 1 + k, rows);
+                    ix[k] = mirror_index(int(fx) - 1 + k, cols);
+                }
             }
         }
-    }
-    for (int64_t b = blockIdx.z; b < batch; b += gridDim.z) {
-        T v = T(0);
-        if (inside) {
-            const T* cb = coeff + b * int64_t(rows) * cols;
-            T acc = T(0);
+        for (int64_t b = blockIdx.z; b < batch; b += gridDim.z) {
+            T v = T(0);
+            if (inside) {
+                const T* cb = coeff + b * int64_t(rows) * cols;
+                T acc = T(0);
 #pragma unroll
-            for (int ky = 0; ky < 4; ++ky) {
-                const T* crow = cb + int64_t(iy[ky]) * cols;
-                T racc = T(0);
+                for (int ky = 0; ky < 4; ++ky) {
+                    const T* crow = cb + int64_t(iy[ky]) * cols;
+                    T racc = T(0);
 #pragma unroll
-                for (int kx = 0; kx < 4; ++kx) racc += T(wx[kx]) * crow[ix[kx]];
-                acc += T(wy[ky]) * racc;
+                    for (int kx = 0; kx < 4; ++kx) racc += T(wx[kx]) * crow[ix[kx]];
+                    acc += T(wy[ky]) * racc;
+                }
+                v = T(scale) * acc;
             }
-            v = T(scale) * acc;
+            out[b * out_bstride + int64_t(r) * out_ld + c] = v;
         }
-        out[b * out_bstride + int64_t(r) * out_ld + c] = v;
     }
 }
 
@@ -201,8 +214,10 @@ size_t warp_ws_bytes(int32_t dtype, int64_t batch, int64_t rows, int64_t cols) {
 
 bool real_or_complex(int32_t dtype) { return dtype == PM_F32 || dtype == PM_F64 || dtype == PM_C64 || dtype == PM_C128; }
 
+// every kernel here steps over the rows (row_step, the tile loop of spline_fir_kernel) and the stack members that the caps leave out
 dim3 grid_of(int64_t cols, int64_t rows, int64_t batch, dim3 block) {
-    return dim3(unsigned((cols + block.x - 1) / block.x), unsigned((rows + block.y - 1) / block.y),
+    const int64_t gy = (rows + block.y - 1) / block.y;
+    return dim3(unsigned((cols + block.x - 1) / block.x), unsigned(gy < kMaxGridY ? gy : kMaxGridY),
                 unsigned(batch < kMaxGridZ ? batch : kMaxGridZ));
 }
 

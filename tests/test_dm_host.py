@@ -3,7 +3,6 @@ declared / exported / bound symbols, argument errors, lattice geometry and homog
 model of the kernels' formulation (separable FIR prefilter + 4 x 4 taps, constant mode) against scipy and the fixture."""
 import ctypes
 import json
-import math
 import os
 
 import numpy as np
@@ -11,6 +10,8 @@ import pytest
 from scipy import ndimage
 
 from conftest import GOLDEN
+import dm_common as DC
+from dm_common import model_sample
 
 SYMS = ('pm_lattice', 'pm_warp', 'pm_warp_workspace')
 
@@ -135,46 +136,6 @@ def test_homographies_match_fixture(fx):
 
 # ----------------------------------------------------------------------------- the kernels' formulation in numpy
 
-Z = math.sqrt(3) - 2
-
-
-def _mirror(i, n):
-    if n == 1:
-        return np.zeros_like(i)
-    p = 2 * n - 2
-    i = np.mod(i, p)
-    return np.where(i > n - 1, p - i, i)
-
-
-def _fir(a, axis, K):
-    n = a.shape[axis]
-    out = np.zeros_like(a)
-    for k in range(-K, K + 1):
-        out += math.sqrt(3) * Z ** abs(k) * np.take(a, _mirror(np.arange(n) + k, n), axis=axis)
-    return out
-
-
-def _weights(t):
-    u = 1 - t
-    return [u ** 3 / 6, 2 / 3 - t * t + t ** 3 / 2, 2 / 3 - u * u + u ** 3 / 2, t ** 3 / 6]
-
-
-def model_sample(img, yy, xx, K=30):
-    """pm_warp's arithmetic: FIR prefilter (2K + 1 taps, mirror), 4 x 4 taps with mirrored indices, exact 0 outside [0, n - 1]."""
-    c = _fir(_fir(img, 0, K), 1, K)
-    m, n = img.shape
-    inside = (yy >= 0) & (yy <= m - 1) & (xx >= 0) & (xx <= n - 1)
-    fy, fx = np.floor(yy), np.floor(xx)
-    wy, wx = _weights(yy - fy), _weights(xx - fx)
-    out = np.zeros(yy.shape)
-    for a in range(4):
-        iy = _mirror(fy.astype(int) - 1 + a, m)
-        for b in range(4):
-            ix = _mirror(fx.astype(int) - 1 + b, n)
-            out += wy[a] * wx[b] * c[iy, ix]
-    return np.where(inside, out, 0.0)
-
-
 @pytest.mark.parametrize('shape', [(5, 7), (1, 6), (2, 3), (40, 33)])
 def test_model_matches_map_coordinates(shape):
     rng = np.random.default_rng(sum(shape))
@@ -235,3 +196,91 @@ def test_model_render_matches_fixture(fx, name):
     ref = d[f'{name}_wfe']
     assert got.shape == ref.shape
     assert np.max(np.abs(got - ref)[keep]) <= 1e-12 * np.max(np.abs(ref))
+
+
+# ----------------------------------------------------------------------------- the references of tests/test_gpu_dm_kernels.py
+
+WARP_CASES = DC.warp_cases()
+
+
+def _case_id(c):
+    (m, n), name, (om, on), off = c
+    return f'{m}x{n} {name} {om}x{on}@{off[0]},{off[1]}'
+
+
+@pytest.mark.parametrize('case', WARP_CASES, ids=_case_id)
+def test_warp_reference_is_model_through_window(case):
+    """the scipy reference of the entry point against the kernels' arithmetic composed with the window rule, to 1e-14 of
+    max|img| |scale| (the scale of the GPU bounds), on white noise, at every case of the GPU file; an exact zero of one is one of the other"""
+    shape, name, out_shape, off = case
+    rng = np.random.default_rng(shape[0] * 1000 + shape[1])
+    img = rng.standard_normal(shape)
+    H = DC.homography(name, shape)
+    ref = DC.warp_reference(img, H, out_shape, off, -0.5)
+    got = DC.model_warp(img, H, out_shape, off, -0.5)
+    assert ref.shape == got.shape == tuple(out_shape)
+    assert np.max(np.abs(got - ref), initial=0) <= 1e-14 * 0.5 * np.max(np.abs(img))
+    assert np.array_equal(got == 0, ref == 0)
+    # outside the rows x cols grid the window rule gives 0 whatever the homography
+    R, C, _, _ = DC.pull_coordinates(H, out_shape, off)
+    assert not ref[(R < 0) | (R >= shape[0]) | (C < 0) | (C >= shape[1])].any()
+
+
+@pytest.mark.parametrize('case', WARP_CASES, ids=_case_id)
+def test_near_cutoff_share(case):
+    shape, name, out_shape, off = case
+    exact, make = DC.HOMOGRAPHIES[name]
+    H = make(shape)
+    out = DC.left_out(shape, name, out_shape, off)
+    assert out.shape == tuple(out_shape)
+    if not exact:
+        assert np.array_equal(out, DC.near_cutoff(shape, H, out_shape, off))
+        assert out.sum() <= 1e-3 * out.size
+        return
+    # an exact homography leaves nothing out, because float64 holds every coordinate it gives: H is affine with entries that are
+    # multiples of 2^-40, so 2^40 (x, y) is an integer that int64 arithmetic gives without rounding
+    assert not out.any()
+    assert np.array_equal(H[2], [0, 0, 1])
+    Hi = np.rint(H * 2.0 ** 40).astype(np.int64)
+    assert np.array_equal(Hi.astype(np.float64) * 2.0 ** -40, H)
+    R, C, xx, yy = DC.pull_coordinates(H, out_shape, off)
+    for v, row in ((xx, Hi[0]), (yy, Hi[1])):
+        want = row[0] * C + row[1] * R + row[2]
+        scaled = v * 2.0 ** 40
+        assert np.array_equal(scaled, np.floor(scaled)) and np.array_equal(scaled.astype(np.int64), want)
+
+
+def test_exact_homographies_reach_the_cutoff():
+    """what the cutoff cases of the GPU file rely on: a translation by 2^-40 puts exactly one column or row outside, and the identity none"""
+    for shape in DC.CUTOFF_SHAPES:
+        m, n = shape
+        for name, lost in (('identity', 0), ('x-2^-40', m), ('x+2^-40', m), ('y-2^-40', n), ('y+2^-40', n)):
+            _, _, xx, yy = DC.pull_coordinates(DC.homography(name, shape), shape, (0, 0))
+            outside = (xx < 0) | (xx > n - 1) | (yy < 0) | (yy > m - 1)
+            assert outside.sum() == lost, (shape, name)
+
+
+def test_lattice_reference_against_loops():
+    from prysm_amd import _lib as L
+    rng = np.random.default_rng(4)
+    for rows, cols, ny, nx, y0, x0, sy, sx in ((7, 9, 2, 3, 1, 2, 4, 3), (4, 4, 2, 2, 0, 1, 3, 2)):
+        a = rng.integers(-9, 10, (2, ny, nx)).astype(np.float64)
+        want = np.zeros((2, rows, cols))
+        for b in range(2):
+            for i in range(ny):
+                for j in range(nx):
+                    want[b, y0 + i * sy, x0 + j * sx] = -2 * a[b, i, j]
+        got = DC.lattice_reference(L.PM_LATTICE_SCATTER, a, rows, cols, ny, nx, y0, x0, sy, sx, -2)
+        assert np.array_equal(got, want)
+        f = rng.integers(-9, 10, (2, rows, cols)).astype(np.float64)
+        want = np.empty((2, ny, nx))
+        for b in range(2):
+            for i in range(ny):
+                for j in range(nx):
+                    want[b, i, j] = 0.5 * f[b, y0 + i * sy, x0 + j * sx]
+        assert np.array_equal(DC.lattice_reference(L.PM_LATTICE_GATHER, f, rows, cols, ny, nx, y0, x0, sy, sx, 0.5), want)
+
+
+def test_lattice_geometries_fit():
+    for name, (rows, cols, ny, nx, y0, x0, sy, sx, _) in DC.LATTICES.items():
+        assert 0 <= y0 and y0 + (ny - 1) * sy < rows and 0 <= x0 and x0 + (nx - 1) * sx < cols, name
