@@ -648,6 +648,86 @@ int pm_optym_softmax_backprop(int32_t dtype, int64_t rows, int64_t K, const void
  * their adjoints, the adjoints as gathers.  in and out must differ. */
 int pm_optym_spatial_gradient(int32_t dtype, int32_t op, int64_t m, int64_t n, const void* in, void* out, void* stream);
 
+/* L-BFGS-B (csrc/lbfgsb.hip): the passes over the n variables of one step of PrysmLBFGSB (prysm/x/optym/_prysm_lbfgsb.py:206-1108).
+ * REAL data, PM_F32 or PM_F64, arrays taken flat; sums in double, two-stage, no atomics.  The history S, Y is (ring, n) row-major,
+ * rows `ld` apart, a ring in PHYSICAL order: logical pair j < k (oldest first) is row (start + j) % ring.  W = [Y, theta S] has 2k
+ * rows q (q < k: Y's pair q; q >= k: S's pair q - k); results are in that order and WITHOUT theta.  k above PM_LBFGSB_MAX_MEMORY is
+ * PM_ERR_UNSUPPORTED before any launch.  `record`: DEVICE doubles the pass's sums are left in (NULL: no fold launch, the partials stay in the workspace for pm_lbfgsb_small); `workspace`: pm_lbfgsb_workspace()
+ * DEVICE bytes; both 8-byte aligned.  A pass is one launch over n and one fold launch.  prysm_amd/x/lbfgsb_plan.py is the same
+ * arithmetic in numpy and unpacks the records. */
+enum { PM_LBFGSB_MAX_MEMORY = 32, PM_LBFGSB_TILE = 8, PM_LBFGSB_THREADS = 256, PM_LBFGSB_WGS = 1024, PM_LBFGSB_GRAM_WGS = 256 };
+enum { PM_LBFGSB_DIRECTION = 0, PM_LBFGSB_RESIDUAL = 1, PM_LBFGSB_SUBSPACE = 2 };
+enum { PM_LBFGSB_SMALL_DIRECTION = 0, PM_LBFGSB_SMALL_BREAK = 1, PM_LBFGSB_SMALL_RESIDUAL = 2, PM_LBFGSB_SMALL_SUBSPACE = 3, PM_LBFGSB_SMALL_UPDATE = 4 };
+size_t pm_lbfgsb_workspace(void);
+
+/* The small algebra, everything of size 2k x 2k, in double, ONE single-workgroup launch per use (the compact form, lines 316-345;
+ * _WM, 362-407; _Hg, 424-437; _subspace_solve, 856-899; _update_history, 979-1007).  `state`: pm_lbfgsb_state_doubles(memory) DEVICE
+ * doubles that live as long as the optimizer, zero at the start except theta = 1 at [3 memory^2]: S S^T, S Y^T ([i][j] = s_i . y_j)
+ * and Y Y^T, memory x memory each, in LOGICAL order, then theta.  The launch first adds the first-stage partials the pass before it
+ * left in its workspace (that pass called with record = NULL: `partials` is that workspace, nparts its workgroups,
+ * min(PM_LBFGSB_WGS, ceil(n / 256))), then by op:
+ * DIRECTION (after pm_lbfgsb_dots of g): coef = the rows' weights of (1 / theta^2) W N^-1 W^T g, N = -M + W^T W / theta from the
+ *   maintained Gram matrices; record[0] = g . g.
+ * BREAK (after pm_lbfgsb_breakpoints): record = [row . d0 (2k) | d0 . d0, count t <= 0, count finite t > 0 | theta | M (2k x 2k)].
+ * RESIDUAL (no pass before it): coef = the rows' weights of -W M^-1 c, c = c_in (2k DEVICE doubles).
+ * SUBSPACE (after pm_lbfgsb_dots of r under the mask, and pm_lbfgsb_gram with record = NULL into `gram_partials`, gram_parts =
+ *   min(PM_LBFGSB_GRAM_WGS, ceil(n / 256)) its workgroups, or 0 to take the maintained Gram: no variable is active): coef for dx.
+ * UPDATE (after pm_lbfgsb_update): the curvature test, the new row and column of the three Gram matrices (a full history drops
+ *   its oldest pair), theta rounded to dtype; record = [accepted, s . s, s . y, y . y, theta].  The ring's k and start are the caller's.
+ * coef: 2k DEVICE doubles.  memory above PM_LBFGSB_MAX_MEMORY is PM_ERR_UNSUPPORTED. */
+size_t pm_lbfgsb_state_doubles(int32_t memory);
+int pm_lbfgsb_small(int32_t dtype, int32_t op, int32_t memory, int32_t k, int32_t nparts, int32_t gram_parts, void* state, const void* c_in,
+                    void* coef, void* record, const void* partials, const void* gram_partials, void* stream);
+
+/* row_q . v for the 2k rows (W^T g of _Hg, line 435; W_F^T r of _subspace_solve, line 887, under the byte mask `mask`, NULL = all)
+ * and v . w (v . v with w NULL; phi' = g_new . p with k = 0).  record, per tile T of PM_LBFGSB_TILE rows, 9 doubles: the tile's 8
+ * products, then (tile 0) v . w; max(1, ceil(2k / 8)) tiles. */
+int pm_lbfgsb_dots(int32_t dtype, int64_t n, const void* S, const void* Y, int64_t ld, int32_t ring, int32_t start, int32_t k, const void* v,
+                   const void* w, const void* mask, void* record, void* workspace, size_t workspace_bytes, void* stream);
+
+/* _compute_breakpoints (lines 477-507) and the seed of _cauchy (lines 565-609) in one pass: t_i by the reference's sign and finiteness
+ * rules (lower, upper: infinite where there is no bound), d0 = -g where t_i > 0 and 0 elsewhere -- the variables with t_i = 0 are
+ * segments of zero length and leave the path at once -- both stored.  record, per tile 11 doubles: row . d0 of the tile's 8 rows, then
+ * (tile 0) d0 . d0, the count of t_i <= 0, the count of finite t_i > 0. */
+int pm_lbfgsb_breakpoints(int32_t dtype, int64_t n, const void* S, const void* Y, int64_t ld, int32_t ring, int32_t start, int32_t k, const void* x,
+                          const void* g, const void* lower, const void* upper, void* t, void* d0, void* record, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* The history update (step, lines 1086-1096, and _update_history, lines 979-1007): s = alpha p (xt NULL) or s = xt - x (the clipped
+ * trial point), y = g_new - g, formed in the pass and stored into row `slot` of S and Y (not a live row), dotted with every live row
+ * and with each other.  record, per tile 19 doubles: (row . s, row . y) of the tile's 8 rows, then (tile 0) s . s, s . y, y . y.  The
+ * curvature test and the ring's bookkeeping are the caller's. */
+int pm_lbfgsb_update(int32_t dtype, int64_t n, void* S, void* Y, int64_t ld, int32_t ring, int32_t start, int32_t k, int32_t slot, const void* xt,
+                     const void* x, const void* p, double alpha, const void* g_new, const void* g, void* record, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
+/* W_F^T W_F (line 883) without theta: the products of all row pairs over the variables whose mask byte is set (NULL = all), in
+ * 8 x 8 blocks.  record: 64 doubles per tile pair (ti <= tj, counted row by row), [r * 8 + c] = row (8 ti + r) . row (8 tj + c).
+ * k >= 1. */
+int pm_lbfgsb_gram(int32_t dtype, int64_t n, const void* S, const void* Y, int64_t ld, int32_t ring, int32_t start, int32_t k, const void* mask,
+                   void* record, void* workspace, size_t workspace_bytes, void* stream);
+
+/* out = a v + b (u1 - u2) + sum_q coef[q] row_q (coef: 2k DEVICE doubles), accumulated in double and rounded at the store.
+ * PM_LBFGSB_DIRECTION: out = p, e.g. -H g (_Hg, lines 430-437).  PM_LBFGSB_RESIDUAL: out = r (lines 856-863), no record.
+ * PM_LBFGSB_SUBSPACE: the value is dx on the free set (mask) and 0 elsewhere (lines 893-903); x_hat = xc + dx, x_bar = clip(x_hat),
+ * out = x_bar - x, out2 = x_hat - x (lines 1045-1061).  record, 5 doubles: g . out, the count of out != 0, g . out2, the count of
+ * out2 != 0, the minimum of _max_alpha_inside_box's bound_alpha for out2 (lines 906-926; the last three 0, 0, inf for DIRECTION). */
+int pm_lbfgsb_combine(int32_t dtype, int32_t mode, int64_t n, const void* S, const void* Y, int64_t ld, int32_t ring, int32_t start, int32_t k,
+                      double a, const void* v, double b, const void* u1, const void* u2, const void* coef, const void* mask, const void* xc,
+                      const void* x, const void* lower, const void* upper, const void* g, void* out, void* out2, void* record, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/* The Cauchy point write (lines 746-775): visited (t_i <= t_last) variables get xc = x - t g and a 0 byte in free_mask, the others
+ * xc = x + t_stop (-g) and a 1.  One launch. */
+int pm_lbfgsb_cauchy_point(int32_t dtype, int64_t n, const void* x, const void* g, const void* t, double t_last, double t_stop, void* xc,
+                           void* free_mask, void* stream);
+
+/* The trial point xt = x + alpha p (_wolfe_eval, line 25).  With lower and upper it is clipped into the box: the reference clips
+ * only the accepted point (lines 1088-1093) and evaluates the search's other trial points unclipped; here every trial point is
+ * clipped, so the accepted one IS x_new and g_new belongs to it. */
+int pm_lbfgsb_trial(int32_t dtype, int64_t n, const void* x, const void* p, double alpha, const void* lower, const void* upper, void* xt,
+                    void* stream);
+
 /* Thin-film multilayers (csrc/thinfilm.hip): prysm/thinfilm.py and the core of prysm/x/coatings (stack.py, diff.py).  One thread per
  * sample k < K walks the L layers (ambient side first) in registers.  dtype PM_C64 or PM_C128; real operands are of the matching real
  * type.  Operands, all DEVICE arrays: wvl (wavelength) and theta (the ambient angle, RADIANS), real; n0 (ambient index) and nsub

@@ -36,6 +36,9 @@ PM_CFA_RGGB, PM_CFA_BGGR = 0, 1
 PM_BAYER_COMPOSITE, PM_BAYER_RECOMPOSITE = 0, 1
 PM_BAYER_MOSAIC, PM_BAYER_RGB = 0, 1
 PM_COST_MSE, PM_COST_BGI, PM_COST_NLL = 0, 1, 2
+PM_LBFGSB_MAX_MEMORY, PM_LBFGSB_TILE, PM_LBFGSB_THREADS, PM_LBFGSB_WGS, PM_LBFGSB_GRAM_WGS = 32, 8, 256, 1024, 256
+PM_LBFGSB_DIRECTION, PM_LBFGSB_RESIDUAL, PM_LBFGSB_SUBSPACE = 0, 1, 2
+PM_LBFGSB_SMALL_DIRECTION, PM_LBFGSB_SMALL_BREAK, PM_LBFGSB_SMALL_RESIDUAL, PM_LBFGSB_SMALL_SUBSPACE, PM_LBFGSB_SMALL_UPDATE = 0, 1, 2, 3, 4
 PM_OPT_GD, PM_OPT_ADAGRAD, PM_OPT_RMSPROP, PM_OPT_ADAM, PM_OPT_RADAM, PM_OPT_ADAMOMENTUM, PM_OPT_YOGI = 0, 1, 2, 3, 4, 5, 6
 PM_ACT_TANH, PM_ACT_ARCTAN, PM_ACT_SOFTPLUS, PM_ACT_SIGMOID = 0, 1, 2, 3
 PM_GRAD_FORWARD_X, PM_GRAD_ADJOINT_X, PM_GRAD_FORWARD_Y, PM_GRAD_ADJOINT_Y = 0, 1, 2, 3
@@ -183,6 +186,17 @@ SIGNATURES = {
     'pm_optym_softmax': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_vp, c_f64, c_f64, c_vp, c_vp]),
     'pm_optym_softmax_backprop': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_vp, c_f64, c_vp, c_vp]),
     'pm_optym_spatial_gradient': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    'pm_lbfgsb_workspace': (c_sz, []),
+    'pm_lbfgsb_state_doubles': (c_sz, [c_i32]),
+    'pm_lbfgsb_small': (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'pm_lbfgsb_dots': (c_i32, [c_i32, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'pm_lbfgsb_breakpoints': (c_i32, [c_i32, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'pm_lbfgsb_update': (c_i32, [c_i32, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'pm_lbfgsb_gram': (c_i32, [c_i32, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'pm_lbfgsb_combine': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_f64, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'pm_lbfgsb_cauchy_point': (c_i32, [c_i32, c_i64, c_vp, c_vp, c_vp, c_f64, c_f64, c_vp, c_vp, c_vp]),
+    'pm_lbfgsb_trial': (c_i32, [c_i32, c_i64, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp]),
     'pm_tf_stack': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'pm_tf_thickness_grad_workspace': (c_sz, [c_i32, c_i32, c_i64, c_i64]),

@@ -17,7 +17,8 @@ Constructors and step() are the reference's: `fg` (a callable x -> (f, g) or an 
   captured iteration starts from a defined state after reset().
 - RAdam keeps x in its own dtype (the reference's Python-float r promotes a float32 x to float64).
 
-The finite-difference Problem and the L-BFGS-B classes of the reference are not part of this package.
+PrysmLBFGSB is in lbfgsb.py.  The finite-difference Problem, the scipy-driver classes LBFGSB / F77LBFGSB / CLBFGSB and
+DampedLeastSquares of the reference are not part of this package.
 """
 import numpy as np
 import torch
