@@ -910,6 +910,70 @@ int64_t pm_psf_size_groups(int64_t rows);
 int pm_psf_size(int32_t dtype, int64_t rows, int64_t cols, const void* polar, int64_t ld, const void* r, int32_t relative, double value,
                 int32_t last, void* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The wavefront sensors (csrc/sensors.hip): prysm/x/psi.py, prysm/x/shack_hartmann.py, prysm/x/pdi.py and prysm/x/sri.py.  Every array
+ * is on the DEVICE, the small records are HOST structs read at call time.  No atomics and no reductions: each output sample is a
+ * function of its own inputs, so results are the same bits every run.  The unit is compiled without multiply-add contraction;
+ * prysm_amd/x/sensors_plan.py is the same arithmetic in numpy. */
+enum { PM_PSI_MAX_FRAMES = 32 };
+/* K frames of one shape, each with its own base pointer (separately allocated frames are not stacked; a (K, rows, cols) array gives
+ * frame[k] = base + k * rows * ld), and the scheme's weights.  The kernel receives the table by value in its arguments. */
+typedef struct pm_psi_frames {
+    const void* frame[PM_PSI_MAX_FRAMES];
+    double s[PM_PSI_MAX_FRAMES];
+    double c[PM_PSI_MAX_FRAMES];
+} pm_psi_frames;
+
+/* psi_accumulate and degroot_formalism_psi (psi.py:45-71, 74-109; the two sum_of_2d_modes calls of polynomials/fitting.py:7-37 and the
+ * arctan2): num = sum_k s[k] g_k, den = sum_k c[k] g_k, phase = atan2(num, den) over rows x cols samples, the frames' rows ld apart and
+ * the outputs' rows out_ld apart.  Any of num, den, phase may be NULL, not all three.  1 <= K <= PM_PSI_MAX_FRAMES.  frame_dtype
+ * PM_F32, PM_F64, PM_U8 or PM_U16; the sums run in double over k ascending for every frame dtype and are rounded once to out_dtype
+ * (PM_F32 / PM_F64; the frames' own dtype for float frames), atan2 is taken of the rounded pair in out_dtype.  One launch, every frame
+ * read once: 16-byte loads when every frame lies at the same offset from a 16-byte boundary and ld is a multiple of 16 bytes (a
+ * scalar head and tail per row), element loads otherwise; 16-byte stores under the same rule for the outputs. */
+int pm_psi(int32_t frame_dtype, int32_t out_dtype, int64_t K, int64_t rows, int64_t cols, const pm_psi_frames* frames, int64_t ld, void* num,
+           void* den, void* phase, int64_t out_ld, void* stream);
+
+enum { PM_LENSLET_RECTANGLE = 0, PM_LENSLET_CIRCLE = 1 };
+/* nx x ny lenslets `pitch` apart: centre i along x is T(i - nx / 2) * T(pitch) + T(shift_x), each operation rounded in the working
+ * precision T (make_xy_grid(n, dx=pitch, grid=False) and the += pitch / 2 of shift=True, shack_hartmann.py:83-89), likewise along y.
+ * RECTANGLE: the sample is inside where |x - xc| - half_width <= 0 and |y - yc| - half_height <= 0 (geometry.rectangle at angle 0);
+ * CIRCLE: where rsq - half_width <= 0 with half_width the SQUARED radius (geometry.circle called on r = rsq, shack_hartmann.py:112).
+ * The aperture must stay within one pitch of its centre.  k = -2 pi / (wavelength / 1e3). */
+typedef struct pm_lenslets {
+    int32_t kind, nx, ny, reserved;
+    double pitch, shift_x, shift_y, half_width, half_height, efl, k;
+} pm_lenslets;
+
+/* shack_hartmann (shack_hartmann.py:11-117), the double loop over lenslets as ONE launch: out (ny x nx complex samples of dtype's
+ * precision, rows out_ld apart) = exp(i k total), total = the sum over the lenslets whose aperture holds the sample of
+ * ((x - xc)^2 + (y - yc)^2) / (2 efl), every operation in T.  The reference's windows never clip an aperture, so this windowless sum
+ * over the 3 x 3 lenslets around the nearest centre, added with the rows of lenslets outermost as the reference adds them, is its
+ * result; a sample on the shared edge of two lenslets satisfies <= in both and gets both terms, as there.  coords as
+ * pm_object_render: PM_COORDS_GRID (x = (col - nx / 2) dx, y = (row - ny / 2) dx), PM_COORDS_SEPARABLE (x: nx values; y: ny values ldy
+ * elements apart) or PM_COORDS_POINTWISE (ny x nx arrays, rows ldx / ldy apart). */
+int pm_lenslet_screen(int32_t dtype, int32_t coords, int64_t ny, int64_t nx, const void* x, int64_t ldx, const void* y, int64_t ldy, double dx,
+                      const pm_lenslets* lens, void* out, int64_t out_ld, void* stream);
+
+enum { PM_GRATING_SIN_AMP = 0, PM_GRATING_PULSE = 1 };
+/* The grating of PSPDI (pdi.py:129-149, 215-222) and rectangle_pulse (pdi.py:11-51) in one pass: g at xs = x + shift (shift == 0: x
+ * itself), out = field * g (complex, field rows field_ld apart) or, field NULL, out = g (real).  x through coords as above (only the
+ * first coordinate is read).  p: 5 HOST doubles rounded once to dtype --
+ *   SIN_AMP   g = 1 - ((sin(p0 xs) + 1) / 2) 0.1, p0 = rulings pi / (epd / 2)
+ *   PULSE     xw = mod(xs, p0) with numpy's sign rule; g = p2 where xw < p1, else p3; g = p4 where |xw| < eps of dtype
+ *             (p0 = period, p1 = duty period, p2 = offset + amplitude, p3 = offset - amplitude, p4 = offset) */
+int pm_grating(int32_t dtype, int32_t kind, int32_t coords, int64_t rows, int64_t cols, const void* x, int64_t ldx, double dx, double shift,
+               const double* p, const void* field, int64_t field_ld, void* out, int64_t out_ld, void* stream);
+
+/* The beam combination of the interferometers (pdi.py:235-253, sri.py:171-178): t = ca a + cb b for complex a, b (PM_C64 / PM_C128) and
+ * real ca, cb; intensity = |t|^2 (real) and / or total = t, each stored once; one of the two may be NULL. */
+int pm_beam_combine(int32_t dtype, int64_t rows, int64_t cols, const void* a, int64_t lda, double ca, const void* b, int64_t ldb, double cb,
+                    void* intensity, int64_t intensity_ld, void* total, int64_t total_ld, void* stream);
+
+/* The field a single-mode fibre emits (sri.py:62-72): out = efib sqrt(P eta) (cos_phi + i sin_phi), efib real, P (the power at the
+ * facet) and eta (the coupling) DEVICE scalars of dtype read by the kernel -- nothing is read on the host. */
+int pm_fiber_scale(int32_t dtype, int64_t rows, int64_t cols, const void* efib, int64_t efib_ld, const void* power, const void* eta, double cos_phi,
+                   double sin_phi, void* out, int64_t out_ld, void* stream);
+
 /* Segmented apertures (csrc/segmented.hip): CompositeHexagonalAperture.compose_opd (prysm/segmented.py:178-285) and its adjoint.
  * The grid is rows x cols REAL points (dtype PM_F32 / PM_F64, computed in that precision); x, y are the aperture's DEVICE coordinate
  * arrays.  `plan` is a DEVICE array of nseg 80-byte segment records built by prysm_amd/segmented.py (struct pm::SegDesc: int32 y0, x0,

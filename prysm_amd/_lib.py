@@ -54,6 +54,9 @@ PM_OBJECT_SLIT_X, PM_OBJECT_SLIT_Y, PM_OBJECT_BINARY, PM_OBJECT_CROSSED = 1, 2, 
  PM_TFP_MAP_COMPLEX, PM_TFP_AIRY_R, PM_TFP_AIRY_EFIELD_R) = range(12)
 PM_FREQ_GRID, PM_FREQ_VECTORS, PM_FREQ_POINTWISE = 0, 1, 2
 PM_TF_MAX_RECORDS = 16
+PM_PSI_MAX_FRAMES = 32
+PM_LENSLET_RECTANGLE, PM_LENSLET_CIRCLE = 0, 1
+PM_GRATING_SIN_AMP, PM_GRATING_PULSE = 0, 1
 
 c_i32, c_i64, c_f64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
 
@@ -85,6 +88,15 @@ class pm_tf_record(ctypes.Structure):
 class pm_tf_freq(ctypes.Structure):
     _fields_ = [('mode', c_i32), ('shift', c_i32), ('dx', c_f64), ('fx', c_vp), ('fy', c_vp), ('fr', c_vp), ('ldx', c_i64), ('ldy', c_i64),
                 ('ldr', c_i64)]
+
+
+class pm_psi_frames(ctypes.Structure):
+    _fields_ = [('frame', c_vp * PM_PSI_MAX_FRAMES), ('s', c_f64 * PM_PSI_MAX_FRAMES), ('c', c_f64 * PM_PSI_MAX_FRAMES)]
+
+
+class pm_lenslets(ctypes.Structure):
+    _fields_ = [('kind', c_i32), ('nx', c_i32), ('ny', c_i32), ('reserved', c_i32), ('pitch', c_f64), ('shift_x', c_f64), ('shift_y', c_f64),
+                ('half_width', c_f64), ('half_height', c_f64), ('efl', c_f64), ('k', c_f64)]
 
 
 # name -> (restype, argtypes); tests/test_capi_symbols.py checks this table against include/prysm_amd.h
@@ -217,6 +229,11 @@ SIGNATURES = {
     'pm_psf_size_workspace': (c_sz, [c_i64]),
     'pm_psf_size_groups': (c_i64, [c_i64]),
     'pm_psf_size': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i32, c_f64, c_i32, c_vp, c_vp, c_sz, c_vp]),
+    'pm_psi': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_i64, ctypes.POINTER(pm_psi_frames), c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'pm_lenslet_screen': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_f64, ctypes.POINTER(pm_lenslets), c_vp, c_i64, c_vp]),
+    'pm_grating': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_f64, c_f64, ctypes.POINTER(c_f64), c_vp, c_i64, c_vp, c_i64, c_vp]),
+    'pm_beam_combine': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i64, c_f64, c_vp, c_i64, c_f64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    'pm_fiber_scale': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_f64, c_f64, c_vp, c_i64, c_vp]),
     'pm_segment_plan_check': (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64]),
     'pm_segment_compose': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                    c_vp, c_i32, c_vp, c_vp]),

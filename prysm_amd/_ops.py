@@ -1087,3 +1087,74 @@ def psf_size(polar, r, relative, value, last):
                             polar.stride(0) if rows > 1 else cols, L.ptr(r), int(relative), float(value), int(last), L.ptr(out), L.ptr(ws),
                             nbytes, L.stream_ptr()))
     return out
+
+
+# --------------------------------------------------------------------------- the wavefront sensors (csrc/sensors.hip)
+
+_FRAME_CODE = {torch.float32: L.PM_F32, torch.float64: L.PM_F64, torch.uint8: L.PM_U8, torch.uint16: L.PM_U16}
+
+
+def _rcode(dtype):
+    return L.PM_F32 if dtype == torch.float32 else L.PM_F64
+
+
+def psi(frames, s, c, out_dtype, want=(True, True, True)):
+    """pm_psi: (num, den, phase) -- None where `want` is False -- of K frames, device tensors of one shape (rows, cols), one dtype and one
+    row stride, each read where it lies (a (K, rows, cols) tensor passes as the list of its planes).  s, c: K host floats."""
+    K = len(frames)
+    f0 = frames[0]
+    rows, cols = f0.shape
+    ld = f0.stride(0) if rows > 1 else cols
+    tab = L.pm_psi_frames()
+    for k, f in enumerate(frames):
+        tab.frame[k] = f.data_ptr()
+        tab.s[k], tab.c[k] = float(s[k]), float(c[k])
+    outs = [torch.empty((rows, cols), dtype=out_dtype, device=f0.device) if w else None for w in want]
+    L.check(L.load().pm_psi(_FRAME_CODE[f0.dtype], _rcode(out_dtype), K, rows, cols, ctypes.byref(tab), ld, L.ptr(outs[0]), L.ptr(outs[1]),
+                            L.ptr(outs[2]), cols, L.stream_ptr()))
+    return tuple(outs)
+
+
+def lenslet_screen(par, dtype, coords, ny, nx, *, x=None, ldx=0, y=None, ldy=0, dx=0.0):
+    """pm_lenslet_screen: the complex screen (ny, nx) of the lenslet array `par` (x/sensors_plan.lenslet_params)"""
+    lens = L.pm_lenslets()
+    for name, v in par.items():
+        setattr(lens, name, v)
+    out = torch.empty((ny, nx), dtype=L._COMPLEX_OF[dtype], device=L.device())
+    L.check(L.load().pm_lenslet_screen(_rcode(dtype), coords, ny, nx, L.ptr(x), ldx, L.ptr(y), ldy, float(dx), ctypes.byref(lens), L.ptr(out), nx,
+                                       L.stream_ptr()))
+    return out
+
+
+def grating(kind, p, dtype, coords, rows, cols, *, x=None, ldx=0, dx=0.0, shift=0.0, field=None):
+    """pm_grating: the grating `kind` with parameters p at x + shift -- real (rows, cols) -- or `field` (complex of dtype) times it"""
+    arr = (ctypes.c_double * 5)(*[float(v) for v in p])
+    fld = 0
+    if field is not None:
+        field = _rows2d(field)
+        fld = field.stride(0) if rows > 1 else cols
+    out = torch.empty((rows, cols), dtype=dtype if field is None else L._COMPLEX_OF[dtype], device=L.device())
+    L.check(L.load().pm_grating(_rcode(dtype), kind, coords, rows, cols, L.ptr(x), ldx, float(dx), float(shift), arr, L.ptr(field), fld, L.ptr(out),
+                                cols, L.stream_ptr()))
+    return out
+
+
+def beam_combine(a, ca, b, cb, want_total=False, want_intensity=True):
+    """pm_beam_combine: (|ca a + cb b|^2, ca a + cb b) of two complex 2-D device tensors of one dtype; None where not wanted"""
+    a, b = _rows2d(a), _rows2d(b)
+    rows, cols = a.shape
+    inten = torch.empty((rows, cols), dtype=L._REAL_OF[a.dtype], device=a.device) if want_intensity else None
+    total = torch.empty((rows, cols), dtype=a.dtype, device=a.device) if want_total else None
+    L.check(L.load().pm_beam_combine(L.code(a), rows, cols, L.ptr(a), a.stride(0) if rows > 1 else cols, float(ca), L.ptr(b),
+                                     b.stride(0) if rows > 1 else cols, float(cb), L.ptr(inten), cols, L.ptr(total), cols, L.stream_ptr()))
+    return inten, total
+
+
+def fiber_scale(efib, power, eta, phase_shift=0.0):
+    """pm_fiber_scale: efib sqrt(power eta) exp(i phase_shift); power, eta: 0-d (or 1-element) device tensors of efib's dtype"""
+    efib = _rows2d(efib)
+    rows, cols = efib.shape
+    out = torch.empty((rows, cols), dtype=L._COMPLEX_OF[efib.dtype], device=efib.device)
+    L.check(L.load().pm_fiber_scale(_rcode(efib.dtype), rows, cols, L.ptr(efib), efib.stride(0) if rows > 1 else cols, L.ptr(power), L.ptr(eta),
+                                    math.cos(phase_shift), math.sin(phase_shift), L.ptr(out), cols, L.stream_ptr()))
+    return out
