@@ -1084,6 +1084,130 @@ int pm_cgemm_abs2(int32_t dtype, int32_t opA, int32_t opB, int64_t M, int64_t N,
                   int64_t lda, const void* B, int64_t ldb, void* R, int64_t ldr, double weight, int32_t accumulate, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* --- interferogram: measured maps with invalid pixels (csrc/interferogram.hip) ------------- */
+
+/* A map is a rows x cols window of a real array, rows `ld` elements apart; NaN marks an invalid pixel and +-inf is left out of every
+ * sum, as np.isfinite does in the reference.  Sums are accumulated in double in two stages without atomics: a call repeated on the
+ * same data leaves the same bits.
+ *
+ * The statistics record: PM_IFG_RECORD DEVICE doubles. */
+enum {
+    PM_IFG_N = 0,      /* finite values */
+    PM_IFG_NNAN = 1,   /* NaN values (inf is in neither count) */
+    PM_IFG_SUM = 2,
+    PM_IFG_SUMSQ = 3,
+    PM_IFG_MIN = 4,    /* of the finite values; NaN when there is none */
+    PM_IFG_MAX = 5,
+    PM_IFG_ROW0 = 6,   /* bounding box of the finite values, inclusive; -1 when there is none */
+    PM_IFG_ROW1 = 7,
+    PM_IFG_COL0 = 8,
+    PM_IFG_COL1 = 9,
+    PM_IFG_MEAN = 10,  /* SUM / N */
+    PM_IFG_SAD = 11,   /* sum |z - MEAN| */
+    PM_IFG_M2 = 12,    /* sum (z - MEAN)^2 */
+    PM_IFG_STD = 13,   /* sqrt(M2 / N) */
+    PM_IFG_RMS = 14,   /* sqrt(SUMSQ / N) */
+    PM_IFG_SA = 15,    /* SAD / N */
+    PM_IFG_RECORD = 16
+};
+/* the basis of the low-order fit, as a set of bits */
+enum { PM_IFG_TERM_PISTON = 1, PM_IFG_TERM_X = 2, PM_IFG_TERM_Y = 4, PM_IFG_TERM_R2 = 8 };
+enum { PM_IFG_FILL = 0, PM_IFG_MASK = 1, PM_IFG_CLIP = 2 };
+enum { PM_IFG_WIN_WELCH = 0, PM_IFG_WIN_HANN = 1, PM_IFG_WIN_ARRAY = 2 };
+enum { PM_IFG_LP = 0, PM_IFG_HP = 1, PM_IFG_BP = 2, PM_IFG_BR = 3 };
+enum { PM_IFG_PSD_ABC = 0, PM_IFG_PSD_AB = 1 };
+enum { PM_IFG_IIR_HANN = 1, PM_IFG_IIR_LPF = 2 };
+
+/* x and y of pixel (r, c), used as doubles.  PM_COORDS_GRID generates them: x = T(c - ox) * T(dx), y = T(r - oy) * T(dy) in the data's
+ * type T (make_xy_grid's elements; prysm/coordinates.py:344-378), or with linspace != 0 x = x0 + c dx, y = y0 + r dy in double
+ * (np.linspace; x, y not read).  PM_COORDS_SEPARABLE reads x[c] and y[r * ldy]; PM_COORDS_POINTWISE reads x[r * ldx + c] and
+ * y[r * ldy + c]; both of the data's type. */
+typedef struct pm_ifg_coords {
+    int32_t mode, linspace;
+    const void* x;
+    const void* y;
+    int64_t ldx, ldy;
+    int64_t ox, oy;
+    double dx, dy, x0, y0;
+} pm_ifg_coords;
+
+/* mean, pv, rms, Sa, std of prysm/util.py:7-97 (each an isfinite selection, then one or two numpy reductions), the NaN count of
+ * Interferogram.dropout_percentage (prysm/interferogram.py:708-711) and the bounding box Interferogram.crop looks for
+ * (interferogram.py:815-822), in one record.  Four launches: the first pair leaves N .. MEAN, the second reads MEAN from the device and
+ * leaves SAD .. SA -- a two-pass variance.  A map without a finite value gives counts, NaN statistics and a box of -1; no error.
+ * workspace: pm_ifg_stats_workspace() bytes. */
+size_t pm_ifg_stats_workspace(int64_t rows, int64_t cols);
+int pm_ifg_stats(int32_t dtype, int64_t rows, int64_t cols, const void* data, int64_t ld, void* record, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
+/* Least-squares fit of the terms in `terms` over the finite pixels by the normal equations: polynomials.lstsq([x, y], z) of fit_plane
+ * (prysm/interferogram.py:35-55, prysm/polynomials/fitting.py:103-126), the np.linalg.lstsq of fit_sphere (interferogram.py:58-82)
+ * and the mean of remove_piston (interferogram.py:862-865).  coef: four DEVICE doubles in the order piston, x, y, x^2 + y^2; a term
+ * that is not fitted, or whose pivot falls below eps (largest pivot), gets 0.  Two launches, nothing is read back.
+ * workspace: pm_ifg_fit_workspace() bytes. */
+size_t pm_ifg_fit_workspace(int64_t rows, int64_t cols);
+int pm_ifg_fit(int32_t dtype, int32_t terms, int64_t rows, int64_t cols, const void* data, int64_t ld, const pm_ifg_coords* coords,
+               void* coef, void* workspace, size_t workspace_bytes, void* stream);
+
+/* data -= sum of the terms in `terms` with the coefficients at coef (four DEVICE doubles, as pm_ifg_fit leaves them), on the finite
+ * pixels, in place; the sum is formed in double and the result rounded once (interferogram.py:862-877 remove_piston, remove_tiptilt,
+ * remove_power).  One launch. */
+int pm_ifg_remove(int32_t dtype, int32_t terms, int64_t rows, int64_t cols, void* data, int64_t ld, const pm_ifg_coords* coords,
+                  const void* coef, void* stream);
+
+/* In place.  PM_IFG_FILL: NaN becomes `value` (interferogram.py:797-813 fill; inf stays).  PM_IFG_MASK: NaN where the byte mask (rows
+ * mask_ld apart) is 0 (interferogram.py:879-894 mask).  PM_IFG_CLIP: NaN where |z| > value * record[PM_IFG_STD], the record read on
+ * the device (interferogram.py:965-981 spike_clip: |z|, not |z - mean|).  One launch. */
+int pm_ifg_edit(int32_t dtype, int32_t op, int64_t rows, int64_t cols, void* data, int64_t ld, double value, const void* mask,
+                int64_t mask_ld, const void* record, void* stream);
+
+/* np.gradient(data, dx) with its default edges and the hypot of the two (interferogram.py:1067-1075 slope): gx along the columns, gy
+ * along the rows, gr = hypot(gx, gy); central differences over T(2 dx) inside, one-sided ones over T(dx) on the border; NaN spreads as
+ * in numpy.  Any of gx, gy, gr may be NULL; the outputs' rows are out_ld apart.  At least 2 samples per axis.  One launch. */
+int pm_ifg_slope(int32_t dtype, int64_t rows, int64_t cols, const void* data, int64_t ld, double dx, void* gx, void* gy, void* gr,
+                 int64_t out_ld, void* stream);
+
+/* out = height x window, or the window itself when height is NULL, and s2[0] = sum window^2 (a DEVICE double) from the same pass:
+ * make_window and the first two lines of psd (prysm/interferogram.py:85-145, 175-180).  PM_IFG_WIN_WELCH: 1 - |r / rmax|^alpha with r
+ * the radius of make_xy_grid(shape, dx) in the data's type and rmax its sample at (rows - 1, cols / 2) (window_2d_welch,
+ * interferogram.py:268-286, _rmax_square_array :26-32); PM_IFG_WIN_HANN: np.hanning(rows) (x) np.hanning(cols);
+ * PM_IFG_WIN_ARRAY: the caller's window (rows window_ld apart).  The window is formed in double and the product rounded once.  Two
+ * launches.  workspace: pm_ifg_window_workspace() bytes. */
+size_t pm_ifg_window_workspace(int64_t rows, int64_t cols);
+int pm_ifg_window(int32_t dtype, int32_t kind, int64_t rows, int64_t cols, const void* height, int64_t ld, double dx, double alpha,
+                  const void* window, int64_t window_ld, void* out, int64_t out_ld, void* s2, void* workspace, size_t workspace_bytes,
+                  void* stream);
+/* data /= s2[0] * fs * fs in place, s2 a DEVICE double (interferogram.py:179-182).  One launch. */
+int pm_ifg_psd_scale(int32_t dtype, int64_t rows, int64_t cols, void* data, int64_t ld, const void* s2, double fs, void* stream);
+
+/* The integral behind bandlimited_rms (interferogram.py:190-265): out[0] = spacing^2 sum w_r w_c psd[r, c] over flow <= nu <= fhigh,
+ * w the trapezoid rule's weights (half on the first and last row and column), out[1] = spacing; the caller takes the square root.
+ * coords PM_COORDS_GRID: nu = hypot((c - cols / 2) / (cols dx), (r - rows / 2) / (rows dx)) in double, the radius of psd()'s axes
+ * (fttools.forward_ft_unit, prysm/fttools.py:128-152), spacing 1 / (rows dx); PM_COORDS_POINTWISE: nu read (rows nu_ld apart),
+ * spacing |nu[rows / 2 - 1][cols / 2] - nu[rows / 2][cols / 2]| read on the device -- two samples along axis 0, used for both axes.
+ * ndim = 1: a 1-D spectrum passed as rows x 1, no column weights, one power of the spacing.  out: two DEVICE doubles.  Two launches.
+ * workspace: pm_ifg_band_workspace() bytes. */
+size_t pm_ifg_band_workspace(int64_t rows, int64_t cols);
+int pm_ifg_band(int32_t dtype, int32_t coords, int32_t ndim, int64_t rows, int64_t cols, const void* psd, int64_t ld, const void* nu,
+                int64_t nu_ld, double dx, double flow, double fhigh, void* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* parts = PM_IFG_IIR_HANN | PM_IFG_IIR_LPF: h' = hann2d(rows, cols) x ideal_lpf_iir2d(r, dx, fcn) (interferogram.py:547-565) for
+ * fcn_low into h_low and, when h_high is not NULL, for fcn_high into h_high: the windowed impulse responses designfilt2d transforms
+ * (interferogram.py:568-632).  PM_IFG_IIR_HANN alone: hann2d into h_low; PM_IFG_IIR_LPF alone: the impulse responses without the
+ * window.  r: generated (PM_COORDS_GRID: hypot(T(c - ox) T(r_dx), T(r - oy) T(r_dx))) or read (PM_COORDS_POINTWISE, rows r_ld
+ * apart); the jinc is the Chebyshev series of csrc/fibers_coefs.h in double, the product is rounded once.  One launch. */
+int pm_ifg_iir(int32_t dtype, int32_t parts, int32_t coords, int64_t rows, int64_t cols, const void* r, int64_t r_ld, int64_t oy,
+               int64_t ox, double r_dx, double dx, double fcn_low, double fcn_high, void* h_low, void* h_high, int64_t out_ld,
+               void* stream);
+/* the transfer function of a filter type from |fft2(h')| (interferogram.py:594-630): PM_IFG_LP Hl, PM_IFG_HP 1 - Hl,
+ * PM_IFG_BP 1 - ((1 - Hh) + Hl), PM_IFG_BR (1 - Hh) + Hl; real, or with complex_out complex with a zero imaginary part, the
+ * multiplier of pm_fft2_mul_ifft2.  One launch. */
+int pm_ifg_combine(int32_t dtype, int32_t typ, int32_t complex_out, int64_t rows, int64_t cols, const void* h_low, int64_t low_ld,
+                   const void* h_high, int64_t high_ld, void* out, int64_t out_ld, void* stream);
+
+/* PM_IFG_PSD_ABC: a / (1 + (nu / b)^c); PM_IFG_PSD_AB: a nu^(-b) (interferogram.py:289-330), n values.  One launch. */
+int pm_ifg_psd_model(int32_t dtype, int32_t kind, int64_t n, const void* nu, double a, double b, double c, void* out, void* stream);
+
 /* --- housekeeping ------------------------------------------------------------------------- */
 /* Real-input 2-D spectrum on ANY even width (round 5; prysm/otf.py:28-33 transform_psf, :62-135 the centre-normalised MTF / PTF / OTF
  * take any size through scipy): the real M x N array IS an M x N/2 complex array z[r][j] = x[r][2j] + i x[r][2j+1]; transform that

@@ -57,6 +57,14 @@ PM_TF_MAX_RECORDS = 16
 PM_PSI_MAX_FRAMES = 32
 PM_LENSLET_RECTANGLE, PM_LENSLET_CIRCLE = 0, 1
 PM_GRATING_SIN_AMP, PM_GRATING_PULSE = 0, 1
+(PM_IFG_N, PM_IFG_NNAN, PM_IFG_SUM, PM_IFG_SUMSQ, PM_IFG_MIN, PM_IFG_MAX, PM_IFG_ROW0, PM_IFG_ROW1, PM_IFG_COL0, PM_IFG_COL1, PM_IFG_MEAN,
+ PM_IFG_SAD, PM_IFG_M2, PM_IFG_STD, PM_IFG_RMS, PM_IFG_SA, PM_IFG_RECORD) = range(17)
+PM_IFG_TERM_PISTON, PM_IFG_TERM_X, PM_IFG_TERM_Y, PM_IFG_TERM_R2 = 1, 2, 4, 8
+PM_IFG_FILL, PM_IFG_MASK, PM_IFG_CLIP = 0, 1, 2
+PM_IFG_WIN_WELCH, PM_IFG_WIN_HANN, PM_IFG_WIN_ARRAY = 0, 1, 2
+PM_IFG_LP, PM_IFG_HP, PM_IFG_BP, PM_IFG_BR = 0, 1, 2, 3
+PM_IFG_PSD_ABC, PM_IFG_PSD_AB = 0, 1
+PM_IFG_IIR_HANN, PM_IFG_IIR_LPF = 1, 2
 
 c_i32, c_i64, c_f64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
 
@@ -97,6 +105,11 @@ class pm_psi_frames(ctypes.Structure):
 class pm_lenslets(ctypes.Structure):
     _fields_ = [('kind', c_i32), ('nx', c_i32), ('ny', c_i32), ('reserved', c_i32), ('pitch', c_f64), ('shift_x', c_f64), ('shift_y', c_f64),
                 ('half_width', c_f64), ('half_height', c_f64), ('efl', c_f64), ('k', c_f64)]
+
+
+class pm_ifg_coords(ctypes.Structure):
+    _fields_ = [('mode', c_i32), ('linspace', c_i32), ('x', c_vp), ('y', c_vp), ('ldx', c_i64), ('ldy', c_i64), ('ox', c_i64), ('oy', c_i64),
+                ('dx', c_f64), ('dy', c_f64), ('x0', c_f64), ('y0', c_f64)]
 
 
 # name -> (restype, argtypes); tests/test_capi_symbols.py checks this table against include/prysm_amd.h
@@ -234,6 +247,21 @@ SIGNATURES = {
     'pm_grating': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_f64, c_f64, ctypes.POINTER(c_f64), c_vp, c_i64, c_vp, c_i64, c_vp]),
     'pm_beam_combine': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i64, c_f64, c_vp, c_i64, c_f64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     'pm_fiber_scale': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_f64, c_f64, c_vp, c_i64, c_vp]),
+    'pm_ifg_stats_workspace': (c_sz, [c_i64, c_i64]),
+    'pm_ifg_stats': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    'pm_ifg_fit_workspace': (c_sz, [c_i64, c_i64]),
+    'pm_ifg_fit': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, ctypes.POINTER(pm_ifg_coords), c_vp, c_vp, c_sz, c_vp]),
+    'pm_ifg_remove': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, ctypes.POINTER(pm_ifg_coords), c_vp, c_vp]),
+    'pm_ifg_edit': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_f64, c_vp, c_i64, c_vp, c_vp]),
+    'pm_ifg_slope': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i64, c_f64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'pm_ifg_window_workspace': (c_sz, [c_i64, c_i64]),
+    'pm_ifg_window': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_f64, c_f64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    'pm_ifg_psd_scale': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_f64, c_vp]),
+    'pm_ifg_band_workspace': (c_sz, [c_i64, c_i64]),
+    'pm_ifg_band': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_f64, c_f64, c_f64, c_vp, c_vp, c_sz, c_vp]),
+    'pm_ifg_iir': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_f64, c_f64, c_f64, c_f64, c_vp, c_vp, c_i64, c_vp]),
+    'pm_ifg_combine': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    'pm_ifg_psd_model': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_f64, c_f64, c_f64, c_vp, c_vp]),
     'pm_segment_plan_check': (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64]),
     'pm_segment_compose': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                    c_vp, c_i32, c_vp, c_vp]),

@@ -1158,3 +1158,214 @@ def fiber_scale(efib, power, eta, phase_shift=0.0):
     L.check(L.load().pm_fiber_scale(_rcode(efib.dtype), rows, cols, L.ptr(efib), efib.stride(0) if rows > 1 else cols, L.ptr(power), L.ptr(eta),
                                     math.cos(phase_shift), math.sin(phase_shift), L.ptr(out), cols, L.stream_ptr()))
     return out
+
+
+# --------------------------------------------------------------------------- measured maps with invalid pixels (csrc/interferogram.hip)
+
+def _ld(t):
+    """elements between the rows of a 2-D tensor with unit column stride (one row: its length)"""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def ifg_window2d(t):
+    """a real 2-D device tensor as the unit's kernels address it, in place: unit column stride and rows at least a row apart -- a
+    contiguous array or a view of one such as Interferogram.crop leaves.  Nothing is copied: the edits write through"""
+    if t.dim() != 2 or t.dtype not in (torch.float32, torch.float64) or not t.is_cuda:
+        raise TypeError('a 2-D float32 / float64 device tensor is required')
+    if t.numel() and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
+        raise ValueError('the rows of the map must be contiguous and must not overlap')
+    return t
+
+
+def ifg_coords(dtype, mode, *, x=None, y=None, origin=(0, 0), dx=0.0, linspace=None):
+    """(pm_ifg_coords, tensors to keep alive, the arrays' shapes or None).  GRID: origin (oy, ox) and step dx, or linspace = (x0, dx, y0, dy); SEPARABLE: 1-D x and y;
+    POINTWISE: 2-D x and y"""
+    co = L.pm_ifg_coords()
+    co.mode = mode
+    keep = []
+    shapes = None
+    if mode != L.PM_COORDS_GRID:
+        shapes = (tuple(x.shape), tuple(y.shape))      # as given: checked against the data by ifg_fit / ifg_remove, nothing broadcasts
+    if mode == L.PM_COORDS_GRID:
+        if linspace is not None:
+            co.linspace = 1
+            co.x0, co.dx, co.y0, co.dy = (float(v) for v in linspace)
+        else:
+            co.oy, co.ox = int(origin[0]), int(origin[1])
+            co.dx = co.dy = float(dx)
+    elif mode == L.PM_COORDS_SEPARABLE:
+        x, _ = _vector(x, dtype)
+        y, co.ldy = _vector(y, dtype)
+        if x.stride(0) != 1:
+            x = x.contiguous()
+        co.x, co.y = x.data_ptr(), y.data_ptr()
+        keep += [x, y]
+    else:
+        x, co.ldx = _rows(x, dtype)
+        y, co.ldy = _rows(y, dtype)
+        co.x, co.y = x.data_ptr(), y.data_ptr()
+        keep += [x, y]
+    return co, keep, shapes
+
+
+def _check_coords(co, data):
+    if co[2] is not None:
+        from .interferogram_plan import check_coord_shapes
+        check_coord_shapes(co[2][0], co[2][1], tuple(data.shape))
+
+
+def ifg_stats(data):
+    """pm_ifg_stats: the record of PM_IFG_RECORD float64 values of a 2-D real device tensor, on the device; nothing is read back"""
+    lib = L.load()
+    data = ifg_window2d(data)
+    rows, cols = data.shape
+    rec = torch.empty(L.PM_IFG_RECORD, dtype=torch.float64, device=data.device)
+    nbytes = lib.pm_ifg_stats_workspace(rows, cols)
+    ws = L.workspace(nbytes)
+    L.check(lib.pm_ifg_stats(_rcode(data.dtype), rows, cols, L.ptr(data), _ld(data), L.ptr(rec), L.ptr(ws), nbytes, L.stream_ptr()))
+    return rec
+
+
+def ifg_fit(data, terms, co):
+    """pm_ifg_fit: the four coefficients (piston, x, y, x^2 + y^2) as a float64 device vector; co from ifg_coords"""
+    lib = L.load()
+    data = ifg_window2d(data)
+    _check_coords(co, data)
+    rows, cols = data.shape
+    coef = torch.empty(4, dtype=torch.float64, device=data.device)
+    nbytes = lib.pm_ifg_fit_workspace(rows, cols)
+    ws = L.workspace(nbytes)
+    L.check(lib.pm_ifg_fit(_rcode(data.dtype), int(terms), rows, cols, L.ptr(data), _ld(data), ctypes.byref(co[0]), L.ptr(coef), L.ptr(ws), nbytes,
+                           L.stream_ptr()))
+    return coef
+
+
+def ifg_remove(data, terms, co, coef):
+    """pm_ifg_remove: data -= the chosen terms, on the finite pixels, in place"""
+    data = ifg_window2d(data)
+    _check_coords(co, data)
+    rows, cols = data.shape
+    L.check(L.load().pm_ifg_remove(_rcode(data.dtype), int(terms), rows, cols, L.ptr(data), _ld(data), ctypes.byref(co[0]), L.ptr(coef), L.stream_ptr()))
+    return data
+
+
+def ifg_edit(data, op, value=0.0, mask=None, record=None):
+    """pm_ifg_edit in place: PM_IFG_FILL (NaN -> value), PM_IFG_MASK (NaN where the bool / uint8 mask is false), PM_IFG_CLIP (NaN where
+    |z| > value * record[PM_IFG_STD])"""
+    data = ifg_window2d(data)
+    rows, cols = data.shape
+    mld = 0
+    if mask is not None:
+        mask = L.as_device(mask) if not isinstance(mask, torch.Tensor) else mask.to(data.device)
+        if mask.dtype not in (torch.bool, torch.uint8):
+            mask = mask != 0
+        if tuple(mask.shape) != (rows, cols):
+            raise ValueError(f'the mask has shape {tuple(mask.shape)}, the data {(rows, cols)}')
+        mask = _rows2d(mask)
+        mld = _ld(mask)
+    L.check(L.load().pm_ifg_edit(_rcode(data.dtype), int(op), rows, cols, L.ptr(data), _ld(data), float(value), L.ptr(mask), mld, L.ptr(record),
+                                 L.stream_ptr()))
+    return data
+
+
+def ifg_slope(data, dx):
+    """pm_ifg_slope: (gx, gy, hypot(gx, gy)) of np.gradient(data, dx)"""
+    data = ifg_window2d(data)
+    rows, cols = data.shape
+    gx, gy, gr = (torch.empty((rows, cols), dtype=data.dtype, device=data.device) for _ in range(3))
+    L.check(L.load().pm_ifg_slope(_rcode(data.dtype), rows, cols, L.ptr(data), _ld(data), float(dx), L.ptr(gx), L.ptr(gy), L.ptr(gr), cols, L.stream_ptr()))
+    return gx, gy, gr
+
+
+def ifg_window(kind, shape, dtype, *, height=None, dx=0.0, alpha=4.0, window=None):
+    """pm_ifg_window: (height x window -- the window itself without a height --, S2 as a one-element float64 device tensor)"""
+    lib = L.load()
+    rows, cols = int(shape[0]), int(shape[1])
+    dev = L.device()
+    hld = wld = 0
+    if height is not None:
+        height = ifg_window2d(height)
+        hld = _ld(height)
+    if window is not None:
+        window, wld = _rows(window, dtype)
+        if tuple(window.shape) != (rows, cols):
+            raise ValueError(f'the window has shape {tuple(window.shape)}, the data {(rows, cols)}')
+    out = torch.empty((rows, cols), dtype=dtype, device=dev)
+    s2 = torch.empty(1, dtype=torch.float64, device=dev)
+    nbytes = lib.pm_ifg_window_workspace(rows, cols)
+    ws = L.workspace(nbytes)
+    L.check(lib.pm_ifg_window(_rcode(dtype), int(kind), rows, cols, L.ptr(height), hld, float(dx), float(alpha), L.ptr(window), wld, L.ptr(out), cols,
+                              L.ptr(s2), L.ptr(ws), nbytes, L.stream_ptr()))
+    return out, s2
+
+
+def ifg_psd_scale(data, s2, fs):
+    """pm_ifg_psd_scale: data /= s2[0] * fs * fs in place"""
+    data = ifg_window2d(data)
+    rows, cols = data.shape
+    L.check(L.load().pm_ifg_psd_scale(_rcode(data.dtype), rows, cols, L.ptr(data), _ld(data), L.ptr(s2), float(fs), L.stream_ptr()))
+    return data
+
+
+def ifg_band(psd, flow, fhigh, *, nu=None, dx=0.0):
+    """pm_ifg_band: (integral, spacing) as a float64 device 2-vector.  psd 2-D with nu None (generated from dx) or 2-D; psd 1-D with nu 1-D"""
+    lib = L.load()
+    ndim = psd.dim()
+    p = psd.reshape(-1, 1) if ndim == 1 else psd
+    if ndim == 1 and not p.is_contiguous():
+        p = p.contiguous()
+    p = ifg_window2d(p)
+    rows, cols = p.shape
+    nld = 0
+    if nu is not None:
+        nu = nu.reshape(-1, 1) if nu.dim() == 1 else nu
+        nu, nld = _rows(nu, p.dtype)
+        if tuple(nu.shape) != (rows, cols):
+            raise ValueError(f'the frequencies have shape {tuple(nu.shape)}, the spectrum {(rows, cols)}')
+    out = torch.empty(2, dtype=torch.float64, device=p.device)
+    nbytes = lib.pm_ifg_band_workspace(rows, cols)
+    ws = L.workspace(nbytes)
+    L.check(lib.pm_ifg_band(_rcode(p.dtype), L.PM_COORDS_GRID if nu is None else L.PM_COORDS_POINTWISE, ndim, rows, cols, L.ptr(p), _ld(p), L.ptr(nu), nld,
+                            float(dx), float(flow), float(fhigh), L.ptr(out), L.ptr(ws), nbytes, L.stream_ptr()))
+    return out
+
+
+def ifg_iir(shape, dtype, dx, fcn_low, fcn_high=None, *, r=None, origin=(0, 0), r_dx=0.0, parts=L.PM_IFG_IIR_HANN | L.PM_IFG_IIR_LPF):
+    """pm_ifg_iir: (h'_low, h'_high or None), r generated from (origin, r_dx) or a 2-D array; parts: the window, the impulse response or
+    their product"""
+    rows, cols = int(shape[0]), int(shape[1])
+    dev = L.device()
+    rld = 0
+    if r is not None:
+        r, rld = _rows(r, dtype)
+        if tuple(r.shape) != (rows, cols):
+            raise ValueError(f'the radial coordinate has shape {tuple(r.shape)}, the filter {(rows, cols)}')
+    lo = torch.empty((rows, cols), dtype=dtype, device=dev)
+    hi = torch.empty((rows, cols), dtype=dtype, device=dev) if fcn_high is not None else None
+    L.check(L.load().pm_ifg_iir(_rcode(dtype), int(parts), L.PM_COORDS_GRID if r is None else L.PM_COORDS_POINTWISE, rows, cols, L.ptr(r), rld, int(origin[0]),
+                                int(origin[1]), float(r_dx), float(dx), float(fcn_low), float(fcn_high or 0.0), L.ptr(lo), L.ptr(hi), cols, L.stream_ptr()))
+    return lo, hi
+
+
+def ifg_combine(typ, Hl, Hh=None, complex_out=False):
+    """pm_ifg_combine: the transfer function of a filter type from |fft2(h')|, real or as a complex multiplier"""
+    Hl = _rows2d(Hl)
+    rows, cols = Hl.shape
+    hld = 0
+    if Hh is not None:
+        Hh = _rows2d(Hh)
+        if tuple(Hh.shape) != (rows, cols) or Hh.dtype != Hl.dtype:
+            raise ValueError('the two spectra of a band filter differ in shape or precision')
+        hld = _ld(Hh)
+    out = torch.empty((rows, cols), dtype=L._COMPLEX_OF[Hl.dtype] if complex_out else Hl.dtype, device=Hl.device)
+    L.check(L.load().pm_ifg_combine(_rcode(Hl.dtype), int(typ), int(bool(complex_out)), rows, cols, L.ptr(Hl), _ld(Hl), L.ptr(Hh), hld, L.ptr(out), cols,
+                                    L.stream_ptr()))
+    return out
+
+
+def ifg_psd_model(kind, nu, a, b, c=0.0):
+    """pm_ifg_psd_model: abc_psd / ab_psd of a real device tensor of any shape"""
+    nu = nu.contiguous()
+    out = torch.empty_like(nu)
+    L.check(L.load().pm_ifg_psd_model(_rcode(nu.dtype), int(kind), nu.numel(), L.ptr(nu), float(a), float(b), float(c), L.ptr(out), L.stream_ptr()))
+    return out
