@@ -1208,6 +1208,69 @@ int pm_ifg_combine(int32_t dtype, int32_t typ, int32_t complex_out, int64_t rows
 /* PM_IFG_PSD_ABC: a / (1 + (nu / b)^c); PM_IFG_PSD_AB: a nu^(-b) (interferogram.py:289-330), n values.  One launch. */
 int pm_ifg_psd_model(int32_t dtype, int32_t kind, int64_t n, const void* nu, double a, double b, double c, void* out, void* stream);
 
+/* --- masked modal fitting (csrc/modalfit.hip) ---------------------------------------------- */
+/* lstsq, normalize_modes and orthogonalize_modes of prysm/polynomials/fitting.py:103-187 over a stored basis: K real planes
+ * modes[k * mode_stride + p], p < npts, PM_F32 or PM_F64, K <= PM_MODES_FIT_MAX (more: PM_ERR_UNSUPPORTED).  A point is valid when
+ * (mask == NULL || mask[p] != 0) && (!finite_from_data || isfinite(data[0][p])); mask is bytes.  Validity is a select: a NaN at an
+ * invalid point leaves no trace in any sum, a non-finite value at a valid point propagates.
+ *
+ * The record: pm_modes_record_doubles(K, nrhs) DEVICE doubles,
+ *   [COUNT | RANK | G (K x K, both triangles) | L (K x K, lower) | dropped (K, 1.0 = dropped) | T (K x K) | b (nrhs x K) | coef (nrhs x K)]
+ * so that everything before b depends on K alone. */
+#define PM_MODES_FIT_MAX 128
+#define PM_MODES_REC_COUNT 0
+#define PM_MODES_REC_RANK 1
+#define PM_MODES_REC_G 2
+#define PM_MODES_GRAM 1
+#define PM_MODES_RHS 2
+#define PM_MODES_FACTOR 0
+#define PM_MODES_SOLVE 1
+#define PM_MODES_INVERT 2
+#define PM_MODES_NORMS_STD 3
+#define PM_MODES_NORMS_PTP 4
+#define PM_MODES_LOWER 0
+#define PM_MODES_DIAGONAL 1
+#define PM_MODES_STAT_N 0
+#define PM_MODES_STAT_SUM 1
+#define PM_MODES_STAT_MIN 2
+#define PM_MODES_STAT_MAX 3
+#define PM_MODES_STAT_MEAN 4
+#define PM_MODES_STAT_M2 5
+#define PM_MODES_STAT_STD 6
+#define PM_MODES_STAT_RECORD 7
+size_t pm_modes_record_doubles(int64_t K, int64_t nrhs);
+
+/* COUNT, G = sum_valid m_i m_j (with PM_MODES_GRAM) and b[r][i] = sum_valid m_i data[r] for nrhs >= 0 vectors data[r * data_stride + p]
+ * (with PM_MODES_RHS; COUNT and G are then left as they are, so a prepared fit pays for b only).  Every product and sum in double on
+ * v_mfma_f64_16x16x4_f64 over 16-blocks of modes; two stages in a fixed order, no atomics: a repeated call returns the same bits.
+ * Each stored plane is read once per 16 data vectors.  16-byte loads when npts is a multiple of 4 and every plane starts on a
+ * 16-byte boundary, element-wise otherwise.  workspace: pm_modes_gram_workspace() bytes; it grows with the workgroup count
+ * (one per 1024 points) up to the cap. */
+size_t pm_modes_gram_workspace(int32_t dtype, int64_t K, int64_t npts, int64_t nrhs);
+int pm_modes_gram(int32_t dtype, int32_t parts, int64_t K, int64_t npts, const void* modes, int64_t mode_stride, int64_t nrhs,
+                  const void* data, int64_t data_stride, const void* mask, int32_t finite_from_data, void* record, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
+/* One single-workgroup launch on the record.  PM_MODES_FACTOR: the unpivoted Cholesky G = L L^T in mode order, in double; a mode whose
+ * pivot is not above K eps64 (largest pivot so far) is dropped: its row and column are zero, it is flagged and RANK counts the rest.
+ * PM_MODES_SOLVE: coef[r] = G^-1 b[r] by the two substitutions for the nrhs vectors, dropped modes 0; stored as doubles in the record
+ * and in `dtype` at coef (nrhs x K).  PM_MODES_INVERT: T = L^-1, lower triangular, dropped rows and columns zero.  PM_MODES_NORMS_STD /
+ * _PTP: T = diag(1 / norm) from the pm_modes_stats record at `stats`, norm < 1e-9 -> 1 (normalize_modes' loophole for piston). */
+int pm_modes_small(int32_t dtype, int32_t op, int64_t K, int64_t nrhs, void* record, const void* stats, void* coef, void* stream);
+
+/* out[k][p] = sum_{j <= k} T[k][j] modes[j][p] (PM_MODES_LOWER) or T[k][k] modes[k][p] (PM_MODES_DIAGONAL) with T read from the
+ * record on the device; sums in double, each output rounded once.  zero_outside: points with mask[p] == 0 store 0 (orthogonalize);
+ * otherwise every point is transformed (normalize).  All K values of a point are read before any is stored: out may be modes. */
+int pm_modes_transform(int32_t dtype, int32_t form, int32_t zero_outside, int64_t K, int64_t npts, const void* modes, int64_t mode_stride,
+                       const void* record, const void* mask, void* out, int64_t out_stride, void* stream);
+
+/* Per mode over the points with mask[p] != 0 (all with mask NULL): N, SUM, MIN, MAX, MEAN, then M2 = sum (m - MEAN)^2 in a second
+ * pass that reads MEAN on the device, and STD = sqrt(M2 / N), numpy's population std.  stats: K x PM_MODES_STAT_RECORD DEVICE doubles.
+ * Four launches.  workspace: pm_modes_stats_workspace() bytes. */
+size_t pm_modes_stats_workspace(int64_t K, int64_t npts);
+int pm_modes_stats(int32_t dtype, int64_t K, int64_t npts, const void* modes, int64_t mode_stride, const void* mask, void* stats,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* --- housekeeping ------------------------------------------------------------------------- */
 /* Real-input 2-D spectrum on ANY even width (round 5; prysm/otf.py:28-33 transform_psf, :62-135 the centre-normalised MTF / PTF / OTF
  * take any size through scipy): the real M x N array IS an M x N/2 complex array z[r][j] = x[r][2j] + i x[r][2j+1]; transform that

@@ -65,6 +65,13 @@ PM_IFG_WIN_WELCH, PM_IFG_WIN_HANN, PM_IFG_WIN_ARRAY = 0, 1, 2
 PM_IFG_LP, PM_IFG_HP, PM_IFG_BP, PM_IFG_BR = 0, 1, 2, 3
 PM_IFG_PSD_ABC, PM_IFG_PSD_AB = 0, 1
 PM_IFG_IIR_HANN, PM_IFG_IIR_LPF = 1, 2
+PM_MODES_FIT_MAX = 128
+PM_MODES_REC_COUNT, PM_MODES_REC_RANK, PM_MODES_REC_G = 0, 1, 2
+PM_MODES_GRAM, PM_MODES_RHS = 1, 2
+PM_MODES_FACTOR, PM_MODES_SOLVE, PM_MODES_INVERT, PM_MODES_NORMS_STD, PM_MODES_NORMS_PTP = 0, 1, 2, 3, 4
+PM_MODES_LOWER, PM_MODES_DIAGONAL = 0, 1
+(PM_MODES_STAT_N, PM_MODES_STAT_SUM, PM_MODES_STAT_MIN, PM_MODES_STAT_MAX, PM_MODES_STAT_MEAN, PM_MODES_STAT_M2, PM_MODES_STAT_STD,
+ PM_MODES_STAT_RECORD) = range(8)
 
 c_i32, c_i64, c_f64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
 
@@ -262,6 +269,13 @@ SIGNATURES = {
     'pm_ifg_iir': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_f64, c_f64, c_f64, c_f64, c_vp, c_vp, c_i64, c_vp]),
     'pm_ifg_combine': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     'pm_ifg_psd_model': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_f64, c_f64, c_f64, c_vp, c_vp]),
+    'pm_modes_record_doubles': (c_sz, [c_i64, c_i64]),
+    'pm_modes_gram_workspace': (c_sz, [c_i32, c_i64, c_i64, c_i64]),
+    'pm_modes_gram': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_sz, c_vp]),
+    'pm_modes_small': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    'pm_modes_transform': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'pm_modes_stats_workspace': (c_sz, [c_i64, c_i64]),
+    'pm_modes_stats': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'pm_segment_plan_check': (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64]),
     'pm_segment_compose': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                    c_vp, c_i32, c_vp, c_vp]),

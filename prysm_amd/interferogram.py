@@ -18,6 +18,8 @@ reads per public call:
   filter                1 launch for the windowed impulse responses, one transform with the |.| epilogue per corner frequency,
                         1 launch for the 1 - H combination, then the fft2 x H ifft2 real chain
   slope                 1 launch
+  pvr                   the 37 fringe Zernike planes (1 launch), polynomials.lstsq (4 launches), the projection from coefficients that
+                        stay on the device (pm_zernike_sum, 1 launch), pv and rms (4 launches and 1 host read each): 2 host reads
 
 Coordinates.  The object keeps x and y as (origin index, step) and hands that to the kernels, which generate the coordinates; .x, .y,
 .r and .t materialise arrays on demand (make_xy_grid, cart_to_polar).  As in the reference, coordinates that were never looked at are
@@ -29,7 +31,7 @@ fit_plane fits {x, y} without a piston term; fit_sphere fits {rho^2, 1} on linsp
 spike_clip compares |data|, not |data - mean|, with nsigma std; bandlimited_rms takes the spacing from two samples along axis 0 and uses
 it for both axes; filter transforms unshifted data and returns the real part.
 
-Not here: pvr and polynomials.lstsq (a general masked mode fit), fit_psd, synthesize_surface_from_psd and render_synthetic_surface,
+Not here: fit_psd, synthesize_surface_from_psd and render_synthetic_surface,
 make_random_subaperture_mask, the Zygo readers and writers and save_*, the interferogram() fringe picture and all plotting.
 """
 import math
@@ -348,6 +350,33 @@ class Interferogram(RichData):
         """Strehl ratio of the data as wavefront error (Welford, Aberrations of Optical Systems, Eq. (13.2))."""
         wvl = self.wavelength * 1e3      # um to nm
         return math.exp(-(2 * math.pi * std(self.data) / wvl) ** 2)
+
+    @staticmethod
+    def pvr_check(shape, normalization_radius):
+        """the reference's refusal (interferogram.py:771-774), from the shape alone"""
+        if normalization_radius is None and shape[0] != shape[1]:
+            raise ValueError('pvr: if normalization_radius is None, data must be square')
+
+    def pvr(self, normalization_radius=None):
+        """Peak-to-valley residual (interferogram.py:743-795; C. Evans, "Robust Estimation of PV for Optical Surface Specification and
+        Testing", OF&T 2008, OWA4): the PV of the fit of the fringe Zernikes 1..37 over r <= 1 plus three times the RMS of what the
+        fit leaves.  normalization_radius None: the data must be square and the radius is r[rows - 1, cols // 2], read on the device.
+        The coefficients never leave the device; the only host reads are those of the two statistics."""
+        from .polynomials import fringe_to_nm, lstsq, zernike_nm_seq
+        from .polynomials.zernike import _sum
+        self.pvr_check(self.shape, normalization_radius)
+        r, t = self.r, self.t
+        if normalization_radius is None:
+            normalization_radius = r[self.shape[0] - 1, self.shape[1] // 2]      # _rmax_square_array (interferogram.py:26-32)
+        r = r / normalization_radius
+        outside = r > 1
+        nan = torch.full((), float('nan'), dtype=self.data.dtype, device=self.data.device)
+        data = torch.where(outside, nan, self.data)
+        nms = [fringe_to_nm(j) for j in range(1, 38)]
+        basis = zernike_nm_seq(nms, r, t, norm=False)
+        coefs = lstsq(basis, data)
+        projected = torch.where(outside, nan, _sum(coefs, nms, r, t, False, L.PM_ZERNIKE_POLAR))
+        return pv(projected) + 3 * rms(data - projected)
 
     # ---- edits
     def fill(self, _with=0):

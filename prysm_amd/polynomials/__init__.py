@@ -18,7 +18,8 @@ from .zernike import (zernike_norm, noll_to_nm, fringe_to_nm, nm_to_fringe, nm_t
                       zernike_nm_seq, zernike_sum, zernike_sum_adjoint)
 from .qpoly import (g_qbfs, h_qbfs, f_qbfs, abc_q2d, G_q2d, F_q2d, g_q2d, f_q2d, Q2d_nm_c_to_a_b, Qbfs, Qbfs_seq, Qcon,  # noqa: F401
                     Qcon_seq, Q2d, Q2d_seq, compute_z_Qbfs, compute_z_Q2d, Q2d_sum, Q2d_sum_adjoint, Qcon_sum, Qcon_sum_adjoint)
-from .fitting import sum_of_2d_modes, sum_of_2d_modes_adjoint  # noqa: F401
+from .fitting import (sum_of_2d_modes, sum_of_2d_modes_adjoint, lstsq, normalize_modes, orthogonalize_modes, hopkins,  # noqa: F401
+                      prepare_lstsq, ModalFit)
 from . import cheby as _cheby, dickson as _dickson, hermite as _hermite, jacobi as _jacobi, laguerre as _laguerre, legendre as _legendre, xy as _xy
 from .cheby import *  # noqa: F401,F403
 from .dickson import *  # noqa: F401,F403
@@ -29,7 +30,8 @@ from .legendre import *  # noqa: F401,F403
 from .xy import *  # noqa: F401,F403
 
 __all__ = ['zernike_norm', 'noll_to_nm', 'fringe_to_nm', 'nm_to_fringe', 'nm_to_ansi_j', 'ansi_j_to_nm', 'zernike_nm', 'zernike_nm_seq',
-           'zernike_sum', 'zernike_sum_adjoint', 'sum_of_2d_modes', 'sum_of_2d_modes_adjoint',
+           'zernike_sum', 'zernike_sum_adjoint', 'sum_of_2d_modes', 'sum_of_2d_modes_adjoint', 'lstsq', 'normalize_modes', 'orthogonalize_modes',
+           'hopkins', 'prepare_lstsq', 'ModalFit',
            'g_qbfs', 'h_qbfs', 'f_qbfs', 'abc_q2d', 'G_q2d', 'F_q2d', 'g_q2d', 'f_q2d', 'Q2d_nm_c_to_a_b', 'Qbfs', 'Qbfs_seq', 'Qcon',
            'Qcon_seq', 'Q2d', 'Q2d_seq', 'compute_z_Qbfs', 'compute_z_Q2d', 'Q2d_sum', 'Q2d_sum_adjoint', 'Qcon_sum', 'Qcon_sum_adjoint']
 # the recurrence families (csrc/recur.hip): Jacobi, Chebyshev, Legendre, Hermite, Laguerre, Dickson, XY -- every name their modules export
