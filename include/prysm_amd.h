@@ -606,11 +606,15 @@ enum { PM_GRAD_FORWARD_X = 0, PM_GRAD_ADJOINT_X = 1, PM_GRAD_FORWARD_Y = 2, PM_G
 
 /* mean_square_error (x/optym/cost.py:73-96), bias_and_gain_invariant_error (cost.py:30-70) and negative_loglikelihood (cost.py:99-125)
  * with the mask handling of cost.py:8-27: the cost to `cost`, a DEVICE cell of dtype, and d cost / d M to grad (n values of dtype, zero
- * where the mask is false).  M, D: n values; D may be NULL for PM_COST_NLL, whose target is then d_scalar.  mask: n bytes (nonzero
- * keeps the element) or NULL.  The mask is a predicate, nothing is compacted: the selected count N is one of the sums.  Every sum is
+ * where the mask is false).  M, D: n values; D may be NULL for PM_COST_NLL, whose target is then d_scalar.  mask: n bytes (ANY nonzero
+ * byte keeps the element, 2 and 255 as 1 does) or NULL; an element the mask drops is never used, whatever it holds (NaN, infinity).
+ * The mask is a predicate, nothing is compacted: the selected count N is one of the sums.  Every sum is
  * accumulated in double, per workgroup and then by one workgroup in a fixed order (no atomics: the result is the same bits run after
- * run), and 1/N, alpha, beta and R are formed in double on the device.  PM_COST_MSE and PM_COST_NLL are three launches, PM_COST_BGI
- * four (its second pass carries sum(raw_err^2), so the cost is the reference's sum of squared residuals).  An all-false mask gives a
+ * run), and 1/N, alpha, beta and R are formed in double on the device.  PM_COST_MSE and PM_COST_NLL are three launches (sums, fold,
+ * gradient).  PM_COST_BGI is six: N, sum I, sum D and sum D^2 and their fold, which leaves the two means on the device; a second read
+ * of I and D for sum (I - Imean)(D - Dmean) and sum (I - Imean)^2 -- the sums of CENTRED data, as the reference centres before it
+ * multiplies, so that a pedestal on I or D costs no digits of alpha -- and the fold that forms alpha and beta; the gradient pass, which
+ * carries sum(raw_err^2), and the fold that forms the cost, the reference's sum of squared residuals.  An all-false mask gives a
  * NaN cost and a zero gradient.  workspace: pm_optym_cost_workspace() DEVICE bytes, 8-byte aligned. */
 size_t pm_optym_cost_workspace(void);
 int pm_optym_cost(int32_t dtype, int32_t kind, int64_t n, const void* M, const void* D, double d_scalar, const void* mask, void* cost, void* grad,

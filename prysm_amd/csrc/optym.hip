@@ -7,9 +7,14 @@
 //        one partial per sum in the workspace.  At most kCostWgs workgroups, grid-stride.
 //      fold: ONE workgroup adds the partials in a fixed order (pm_reduce.h fold_partials) and forms the scalars (1/N, alpha, beta, R)
 //        in double on the device.
+//      centred pass (bias and gain invariant only): the covariance and the variance are sums of CENTRED data, as the reference
+//        writes them (Ihat = I - I.mean()).  Pass A keeps N, sum I, sum D and sum D^2, its fold leaves the two means on the device,
+//        this pass reads M, D and the mask again for sum (I - Imean)(D - Dmean) and sum (I - Imean)^2, and its fold forms alpha and
+//        beta.  The one-pass form sum(I D) - sum(I) Dmean loses (mean / spread)^2 eps of alpha to a pedestal, which is what the cost
+//        is meant not to see (csrc/interferogram.hip and csrc/modalfit.hip take their variances in two passes for the same reason).
 //      pass B: the gradient store (zero where the mask is false).  For the bias-and-gain-invariant cost it also carries the partials
-//        of sum(raw_err^2) and a second fold forms R * that sum, so the cost is the reference's sum of squared residuals.
-//    No float atomics, no tickets: the same launch shape adds the same numbers in the same order, run after run.
+//        of sum(raw_err^2) and a last fold forms R * that sum, so the cost is the reference's sum of squared residuals.
+//    No float atomics, no tickets, no host read: the same launch shape adds the same numbers in the same order, run after run.
 //  - pm_optym_advance / pm_optym_step: one step of GradientDescent, AdaGrad, RMSProp, Adam, RAdam, AdaMomentum or Yogi as one
 //    one-thread kernel (the step counter, a device int64, and what depends on it: 1 - beta1^k, 1 - beta2^k, RAdam's rho, r and its
 //    branch, in double) and ONE kernel over the variables: projected gradient, moments, step, clamp; x and the state in place, the
@@ -37,15 +42,16 @@ namespace {
 
 constexpr int kCostThreads = 256;
 constexpr int kCostWgs = 1024;       // most workgroups of a cost pass: as many partials per sum
-constexpr int kCostSums = 6;         // most sums a cost needs (bias and gain invariant)
-constexpr int kScalars = 8;          // doubles at the head of the workspace: 0 N, 1 1/N or R, 2 alpha, 3 beta
+constexpr int kCostSums = 4;         // most sums of pass A (bias and gain invariant: N, sum I, sum D, sum D^2)
+constexpr int kCentredSums = 2;      // sums of the centred pass: sum (I - Imean)(D - Dmean), sum (I - Imean)^2
+constexpr int kScalars = 8;          // doubles at the head of the workspace: 0 N, 1 1/N or R, 2 alpha, 3 beta, 4 Imean, 5 Dmean
 constexpr int kFlatW = 256;          // a flat array is swept as rows of this many elements (pm_sweep.h)
 constexpr int kSoftThreads = 256;
 
-// workspace: [scalars | partials of pass A (kCostWgs x kCostSums) | partials of pass B (kCostWgs)]
-constexpr size_t kWsDoubles = size_t(kScalars) + size_t(kCostWgs) * kCostSums + size_t(kCostWgs);
+// workspace: [scalars | partials of pass A (kCostWgs x kCostSums) | of the centred pass (kCostWgs x kCentredSums) | of pass B (kCostWgs)]
+constexpr size_t kWsDoubles = size_t(kScalars) + size_t(kCostWgs) * kCostSums + size_t(kCostWgs) * kCentredSums + size_t(kCostWgs);
 
-__host__ __device__ constexpr int sums_of(int kind) { return kind == PM_COST_BGI ? 6 : 2; }
+__host__ __device__ constexpr int sums_of(int kind) { return kind == PM_COST_BGI ? kCostSums : 2; }
 
 template <typename T, int KIND>
 __global__ __launch_bounds__(kCostThreads) void cost_sums_kernel(int64_t n, const T* __restrict__ M, const T* __restrict__ D, double dscalar,
@@ -67,9 +73,7 @@ __global__ __launch_bounds__(kCostThreads) void cost_sums_kernel(int64_t n, cons
         } else {
             a[1] = a[1] + m;
             a[2] = a[2] + d;
-            a[3] = a[3] + m * d;
-            a[4] = a[4] + m * m;
-            a[5] = a[5] + d * d;
+            a[3] = a[3] + d * d;
         }
     }
     wg_fold<kCostThreads, FoldSum>(threadIdx.x, a, partial + int64_t(blockIdx.x) * NS);
@@ -93,14 +97,36 @@ __global__ __launch_bounds__(kCostThreads) void cost_fold_kernel(int nparts, con
         sc[1] = inv;
         *cost = T(-inv * s[1]);
     } else {
-        const double Imean = s[1] / N, Dmean = s[2] / N;
-        const double num = s[3] - s[1] * Dmean;       // sum (I - Imean)(D - Dmean)
-        const double den = s[4] - s[1] * Imean;       // sum (I - Imean)^2
-        const double alpha = num / den;
-        sc[1] = 1.0 / s[5];
-        sc[2] = alpha;
-        sc[3] = Dmean - alpha * Imean;
+        sc[1] = 1.0 / s[3];
+        sc[4] = s[1] / N;
+        sc[5] = s[2] / N;
     }
+}
+
+// the centred pass of the bias-and-gain-invariant cost: the means are pass A's, read from the device
+template <typename T>
+__global__ __launch_bounds__(kCostThreads) void cost_centred_kernel(int64_t n, const T* __restrict__ M, const T* __restrict__ D,
+                                                                     const uint8_t* __restrict__ mask, const double* __restrict__ sc,
+                                                                     double* __restrict__ partial) {
+    const double Imean = sc[4], Dmean = sc[5];
+    double a[kCentredSums] = {0.0, 0.0};
+    const int64_t stride = int64_t(gridDim.x) * kCostThreads;
+    for (int64_t i = int64_t(blockIdx.x) * kCostThreads + threadIdx.x; i < n; i += stride) {
+        if (mask && !mask[i]) continue;
+        const double ci = double(M[i]) - Imean, cd = double(D[i]) - Dmean;
+        a[0] = a[0] + ci * cd;
+        a[1] = a[1] + ci * ci;
+    }
+    wg_fold<kCostThreads, FoldSum>(threadIdx.x, a, partial + int64_t(blockIdx.x) * kCentredSums);
+}
+
+__global__ __launch_bounds__(kCostThreads) void cost_centred_fold_kernel(int nparts, const double* __restrict__ partial, double* __restrict__ sc) {
+    double s[kCentredSums];
+    fold_partials<kCostThreads, FoldSum>(threadIdx.x, nparts, partial, 0.0, s);
+    if (threadIdx.x != 0) return;
+    const double alpha = s[0] / s[1];
+    sc[2] = alpha;
+    sc[3] = sc[5] - alpha * sc[4];
 }
 
 template <typename T, int KIND>
@@ -142,12 +168,17 @@ int cost_run(int64_t n, const void* M, const void* D, double dscalar, const void
     const int wgs = reduce_groups(n, kCostThreads, kCostWgs);
     double* sc = ws;
     double* pa = ws + kScalars;
-    double* pb = pa + size_t(kCostWgs) * kCostSums;
+    double* pc = pa + size_t(kCostWgs) * kCostSums;
+    double* pb = pc + size_t(kCostWgs) * kCentredSums;
     const T* m = static_cast<const T*>(M);
     const T* d = static_cast<const T*>(D);
     const uint8_t* mk = static_cast<const uint8_t*>(mask);
     hipLaunchKernelGGL((cost_sums_kernel<T, KIND>), dim3(wgs), dim3(kCostThreads), 0, st, n, m, d, dscalar, mk, pa);
     hipLaunchKernelGGL((cost_fold_kernel<T, KIND>), dim3(1), dim3(kCostThreads), 0, st, wgs, pa, sc, static_cast<T*>(cost));
+    if (KIND == PM_COST_BGI) {
+        hipLaunchKernelGGL(cost_centred_kernel<T>, dim3(wgs), dim3(kCostThreads), 0, st, n, m, d, mk, sc, pc);
+        hipLaunchKernelGGL(cost_centred_fold_kernel, dim3(1), dim3(kCostThreads), 0, st, wgs, pc, sc);
+    }
     hipLaunchKernelGGL((cost_grad_kernel<T, KIND>), dim3(wgs), dim3(kCostThreads), 0, st, n, m, d, dscalar, mk, sc, static_cast<T*>(grad), pb);
     if (KIND == PM_COST_BGI) hipLaunchKernelGGL(cost_fold2_kernel<T>, dim3(1), dim3(kCostThreads), 0, st, wgs, pb, sc, static_cast<T*>(cost));
     return int(hipGetLastError());

@@ -72,8 +72,9 @@ def mean_square_error(M, D, mask=None):
 
 def bias_and_gain_invariant_error(I, D, mask=None):  # noqa: E741
     """The squared residual of D against the least-squares fit alpha I + beta over the kept elements, normalised by sum(D^2), and its
-    gradient 2 R alpha (alpha I + beta - D) (cost.py:30-70).  Four launches: the six sums in one read, the scalars on the device,
-    the gradient with the residual's sum of squares, the cost."""
+    gradient 2 R alpha (alpha I + beta - D) (cost.py:30-70).  Six launches: N, the two sums and sum D^2 in one read and the means on
+    the device, the covariance and variance of the centred data in a second read and alpha, beta on the device, the gradient with
+    the residual's sum of squares, the cost."""
     return _cost('bias_and_gain_invariant_error', L.PM_COST_BGI, I, D, mask)
 
 

@@ -3,7 +3,10 @@ kernels (which are compiled without fused multiply-add contraction).  No device,
 reference's results and what documents the kernels' formulas.
 
 - costs: every element is widened to float64, the sums are float64, the scalars (1/N, alpha, beta, R) are float64 and the results are
-  rounded once to the data's dtype.  A mask is a predicate; nothing is compacted.
+  rounded once to the data's dtype.  A mask is a predicate; nothing is compacted.  The bias-and-gain-invariant cost takes its covariance
+  and variance from CENTRED data, as the reference does (Ihat = I - I.mean()): a first pass leaves the means, a second sums
+  (I - Imean)(D - Dmean) and (I - Imean)^2.  The one-pass form sum(I D) - sum(I) Dmean loses (mean / spread)^2 eps of alpha to a pedestal,
+  which is the very thing the cost is meant not to see.
 - steps: arithmetic in the data's dtype, expression by expression as prysm/x/optym/optimizers.py writes it; the scalars that depend
   on the iteration number (`coefficients`) are float64 and rounded once where they meet the data.
 - softmax: the row maximum is subtracted; the forward sums are in the data's dtype (the kernel adds them in a butterfly over the lanes
@@ -17,12 +20,13 @@ TANH, ARCTAN, SOFTPLUS, SIGMOID = range(4)
 FORWARD_X, ADJOINT_X, FORWARD_Y, ADJOINT_Y = range(4)
 
 # launch constants of the cost passes (csrc/optym.hip kCostThreads, kCostWgs): a first-stage workgroup runs its grid-stride loop
-# ceil(n / (COST_THREADS * COST_WGS)) times at most
-COST_THREADS, COST_WGS, COST_SUMS, COST_SCALARS = 256, 1024, 6, 8
+# ceil(n / (COST_THREADS * COST_WGS)) times at most.  COST_SUMS: most sums of the first pass (N, sum I, sum D, sum D^2 of the bias-and-gain-
+# invariant cost), COST_CENTRED: the sums of its centred pass, and one more of the gradient pass (sum raw_err^2)
+COST_THREADS, COST_WGS, COST_SUMS, COST_CENTRED, COST_SCALARS = 256, 1024, 4, 2, 8
 
 
 def cost_workspace_bytes():
-    return 8 * (COST_SCALARS + COST_WGS * COST_SUMS + COST_WGS)
+    return 8 * (COST_SCALARS + COST_WGS * COST_SUMS + COST_WGS * COST_CENTRED + COST_WGS)
 
 
 def cost(kind, M, D, mask=None):
@@ -45,9 +49,10 @@ def cost(kind, M, D, mask=None):
             c = -inv * np.sum(dk * np.log(mk) + (1.0 - dk) * np.log(1.0 - mk))
             gk = ((-dk / mk) + ((1.0 - dk) / (1.0 - mk))) * inv
         elif kind == COST_BGI:
-            sI, sD, sID, sII, sDD = np.sum(mk), np.sum(dk), np.sum(mk * dk), np.sum(mk * mk), np.sum(dk * dk)
+            sI, sD, sDD = np.sum(mk), np.sum(dk), np.sum(dk * dk)
             Imean, Dmean = sI / N, sD / N
-            alpha = (sID - sI * Dmean) / (sII - sI * Imean)
+            ci, cd = mk - Imean, dk - Dmean
+            alpha = np.sum(ci * cd) / np.sum(ci * ci)
             beta = Dmean - alpha * Imean
             R = np.float64(1.0) / sDD
             raw = (alpha * mk + beta) - dk
@@ -73,14 +78,15 @@ def coefficients(kind, k, beta1, beta2):
     return np.array([1.0 - b1k, 1.0 - b2k, rho, r, flag, np.sqrt(1.0 - b2k), 0.0, 0.0])
 
 
-def step(kind, k, x, g, s1=None, s2=None, lower=None, upper=None, alpha=0.05, beta1=0.9, beta2=0.999, eps=None):
+def step(kind, k, x, g, s1=None, s2=None, lower=None, upper=None, alpha=0.05, beta1=0.9, beta2=0.999, eps=None, coef=None):
     """pm_optym_advance + pm_optym_step out of place: dict(x, s1, s2, x_prev, g_step, active).  k is the number of THIS step (from 1);
-    beta1 is RMSProp's gamma."""
+    beta1 is RMSProp's gamma.  coef: the eight coefficients of the step where they come from elsewhere (read back from the device, whose
+    pow is not numpy's to the bit); what is left of the step is + - * / and sqrt in x's dtype."""
     x = np.asarray(x)
     T = x.dtype.type
     g = np.asarray(g, dtype=x.dtype)
     eps = T(np.finfo(x.dtype).eps if eps is None else eps)
-    co = coefficients(kind, k, beta1, beta2)
+    co = coefficients(kind, k, beta1, beta2) if coef is None else np.asarray(coef, dtype=np.float64)
     al, b1, ob1, b2, ob2 = T(alpha), T(beta1), T(1.0 - beta1), T(beta2), T(1.0 - beta2)
     bounded = lower is not None
     gs = g

@@ -1,6 +1,8 @@
 """CPU: the optym model (prysm_amd/x/optym_plan.py, the numpy restatement of csrc/optym.hip) against the reference's results
 (tests/golden/optym.npz and optym_<Optimizer>_<mode>.npz), the argument checks of the C entry points, the governors and runners on a
-pure-Python optimizer, and the reference's error types."""
+pure-Python optimizer, and the reference's error types; and the cases, references and bounds that tests/test_gpu_optym_kernels.py
+holds the kernels to (tests/optym_common.py), on the model: the centred bias-and-gain-invariant cost against long double at pedestals
+where the one-pass form it replaced fails, the coefficient override of the step, the edges of the activations and of the softmax."""
 import ctypes
 import os
 import re
@@ -8,6 +10,7 @@ import re
 import numpy as np
 import pytest
 
+import optym_common as OC
 from conftest import rel_max
 from prysm_amd.x import optym_plan as OP
 
@@ -389,3 +392,197 @@ def test_the_references_error_types():
     assert np.array_equal(O.DiscreteEncoder(O.Softmax(), 4).levels, np.arange(4))
     t = O.Tanh(2, 1, 3)
     assert (t.a, t.x0, t.y0) == (2, 1, 3) and (O.Sigmoid().a, O.Sigmoid().x0, O.Sigmoid().y0) == (1, 0, 0)
+
+
+# ----------------------------------------------------------------------------- the cases and bounds of tests/test_gpu_optym_kernels.py
+
+def one_pass_bgi(I, D, keep=None):  # noqa: E741
+    """the cost model as it was before the sums were centred: sum(I D) - sum(I) Dmean and sum(I I) - sum(I) Imean in float64"""
+    keep = np.ones(I.shape, bool) if keep is None else keep
+    m, d = I[keep].astype(np.float64), D[keep].astype(np.float64)
+    N = np.float64(m.size)
+    sI, sD, sID, sII, sDD = m.sum(), d.sum(), (m * d).sum(), (m * m).sum(), (d * d).sum()
+    alpha = (sID - sI * (sD / N)) / (sII - sI * (sI / N))
+    beta = sD / N - alpha * (sI / N)
+    raw = (alpha * m + beta) - d
+    g = np.zeros(I.shape)
+    g[keep] = 2.0 * (1.0 / sDD) * alpha * raw
+    return np.asarray((1.0 / sDD) * (raw * raw).sum()).astype(I.dtype), g.astype(I.dtype)
+
+
+@pytest.mark.parametrize('n', OC.COST_SIZES)
+def test_centred_cost_model_meets_the_pedestal_bounds_and_the_one_pass_form_does_not(n):
+    failed_before = set()
+    for dt in OC.DTYPES:
+        name = np.dtype(dt).name
+        for ped in OC.PEDESTALS:
+            I, D, mask = OC.bgi_inputs(ped, n, name)  # noqa: E741
+            for masked in (False, True):
+                keep = mask if masked else None
+                ref = OC.bgi_case(ped, n, name, masked)
+                bg, bc = OC.bgi_bounds(ref, ped, dt)
+                eg, ec = OC.bgi_errors(*OP.cost(OP.COST_BGI, I, D, keep), ref)
+                og, oc = OC.bgi_errors(*one_pass_bgi(I, D, keep), ref)
+                print(f'bgi model {name} n={n} pedestal {ped:g} masked={masked}: gradient {eg:.2e} (one-pass {og:.2e}) bound {bg:.2e}, '
+                      f'cost {ec:.2e} (one-pass {oc:.2e}) bound {bc:.2e}')
+                assert eg <= bg and ec <= bc, (name, ped, masked, eg, bg, ec, bc)
+                if og > bg:
+                    failed_before.add((name, ped))
+            if keep is not None:        # what the mask drops leaves no trace, whatever it holds
+                In, Dn = I.copy(), D.copy()
+                In[~mask], Dn[~mask] = np.nan, np.inf
+                c, g = OP.cost(OP.COST_BGI, In, Dn, mask)
+                c0, g0 = OP.cost(OP.COST_BGI, I, D, mask)
+                assert OC.same_bits(c, c0) and OC.same_bits(g, g0)
+    assert failed_before >= {('float64', 1e2), ('float64', 1e4), ('float32', 1e4)}, failed_before
+
+
+def test_integer_costs_are_exact_in_the_model():
+    for dt in OC.DTYPES:
+        I, D, mask = OC.integer_case(np.dtype(dt).name)  # noqa: E741
+        assert np.array_equal(I, np.round(I)) and np.abs(I).max() <= 8 and np.abs(D).max() <= 8
+        for keep in (None, mask):
+            wc, wg = OC.mse_reference(I, D, keep)
+            c, g = OP.cost(OP.COST_MSE, I, D, keep)
+            # the sum is exact; 1 / N, the product with it and the rounding to the dtype are the model's only roundings
+            assert abs(OC.LD(c) - wc) <= (2 * OC.EPS64 + OC.eps_of(dt)) * wc
+            assert np.abs(g.astype(OC.LD) - wg).max() <= (2 * OC.EPS64 + OC.eps_of(dt)) * np.abs(wg).max()
+        ref = OC.bgi_reference(I, D)
+        c, g = OP.cost(OP.COST_BGI, I, D)
+        # the means are 0 and 1, the centred sums integers: alpha and beta are one division and one product from exact numbers
+        assert abs(float(np.float64(ref['alpha']))) > 1 and np.abs(g.astype(OC.LD) - ref['grad']).max() <= 8 * OC.eps_of(dt) * np.abs(ref['grad']).max()
+        assert abs(OC.LD(c) - ref['cost']) <= (OC.INTEGER_COST_BOUND + OC.eps_of(dt)) * ref['cost']
+
+
+def test_step_model_with_given_coefficients_equals_the_default_path():
+    for dt in OC.DTYPES:
+        case = OC.step_case(257, np.dtype(dt).name)
+        for kind in range(7):
+            x, s1, s2 = case['x'].copy(), np.zeros(257, dt), np.zeros(257, dt)
+            for k in range(1, 8):
+                g = OC.step_gradient(case, x, k)
+                a = OP.step(kind, k, x, g, s1, s2, case['lower'], case['upper'], alpha=0.05, beta1=0.5, beta2=0.9)
+                b = OP.step(kind, k, x, g, s1, s2, case['lower'], case['upper'], alpha=0.05, beta1=0.5, beta2=0.9,
+                            coef=OP.coefficients(kind, k, 0.5, 0.9))
+                for key in OC.STEP_OUTPUTS:
+                    if a[key] is not None:
+                        assert OC.same_bits(np.asarray(a[key]), np.asarray(b[key])), (kind, k, key)
+                # a NaN x and a NaN gradient stay where they are and go nowhere else
+                nan = np.isnan(a['x'])
+                assert nan[case['nan_x']] and (kind != OP.GD or nan[case['nan_g']]) and nan.sum() <= 2
+                assert set(np.unique(a['active'])) <= {False, True}
+                x, s1, s2 = a['x'], a['s1'] if a['s1'] is not None else s1, a['s2'] if a['s2'] is not None else s2
+        # a wrong coefficient is used: the override is not ignored
+        co = OP.coefficients(OP.ADAM, 3, 0.9, 0.999)
+        co[0] *= 2
+        g = OC.step_gradient(case, case['x'], 1)
+        z = np.zeros(257, dt)
+        assert not OC.same_bits(OP.step(OP.ADAM, 3, case['x'], g, z, z, coef=co)['x'], OP.step(OP.ADAM, 3, case['x'], g, z, z)['x'])
+
+
+def test_step_cases_hold_what_they_promise():
+    for n in OC.STEP_SIZES:
+        case = OC.step_case(n, 'float32')
+        lo, hi, x = case['lower'], case['upper'], case['x']
+        assert np.all(np.isneginf(lo) | np.isfinite(lo)) and np.all(np.isposinf(hi) | np.isfinite(hi))
+        if n >= 255:
+            combos = {(bool(np.isfinite(a)), bool(np.isfinite(b))) for a, b in zip(lo, hi)}
+            assert len(combos) == 4 and (x == lo).sum() >= 8 and (x == hi).sum() >= 8
+            gs = [OC.step_gradient(case, x, k) for k in range(1, 5)]
+            for on in (x == lo, x == hi):
+                seen = {s for g in gs for s in np.sign(g[on]).tolist()}
+                assert seen >= {1.0, -1.0, 0.0}
+            assert np.isnan(x).sum() == 1 and all(np.isnan(g).sum() == 2 for g in gs)       # the gradient's own NaN and the one x hands on
+            a, b = case['inf_lo'], case['inf_hi']
+            assert x[a] == -np.inf and lo[a] == -np.inf and x[b] == np.inf and hi[b] == np.inf and all(g[a] > 0 and g[b] < 0 for g in gs)
+            # there the reference's np.isfinite decides: the gradient passes and the bound is not active
+            r = OP.step(OP.ADAM, 1, x, gs[0], np.zeros_like(x), np.zeros_like(x), lo, hi)
+            assert r['g_step'][a] == gs[0][a] and r['g_step'][b] == gs[0][b] and not r['active'][a] and not r['active'][b]
+
+
+def test_coefficient_model_against_long_double():
+    for b1, b2 in OC.BETAS:
+        flags = []
+        for k in OC.ADVANCE_KS:
+            got = OP.coefficients(OP.RADAM, k, b1, b2)
+            want = OC.coefficients_reference(OP.RADAM, k, b1, b2)
+            for i, bound in OC.coefficient_bounds(want, k, b2).items():
+                assert abs(OC.LD(got[i]) - want[i]) <= bound, (b1, b2, k, i)
+            assert got[4] == want[4]
+            flags.append(want[4])
+        assert flags[0] == 0.0 and flags[-1] == 1.0 and flags == sorted(flags)
+
+
+def test_activation_model_at_the_edges():
+    for dt in OC.DTYPES:
+        for a, x0, y0 in OC.ACT_PARAMS:
+            for n in OC.ACT_SIZES:
+                x = OC.activation_input(n, np.dtype(dt).name, a, x0)
+                if n > 1:
+                    with np.errstate(invalid='ignore'):
+                        arg = a * (x.astype(np.float64) - x0)
+                    assert np.isnan(x).sum() == 1 and np.isinf(x).sum() == 2 and (x == 0).sum() >= 2 and np.signbit(x[1]) and not np.signbit(x[0])
+                    assert all(np.any(np.abs(arg - v) < 1e-3 * abs(v)) for v in (100, -100, 1000, -1000))
+                    assert ((x != 0) & (np.abs(x) < np.finfo(dt).tiny)).sum() == 4
+                for kind in range(4):
+                    for back in (False, True):
+                        with np.errstate(all='ignore'):
+                            model = OP.activation(kind, x, a, x0, y0, backprop=back)
+                        want = OC.activation_reference(kind, x, a, x0, y0, back)
+                        assert model.dtype == dt and np.array_equal(np.isnan(model), np.isnan(want))
+                        # the model overflows where the dtype does (softplus of 1000 is inf, in float32 of 100 too): never where it is finite
+                        fin = np.isfinite(model)
+                        assert np.isfinite(want[fin]).all()
+                        err = np.abs(model[fin].astype(OC.LD) - want[fin]) / np.maximum(1, np.abs(want[fin]))
+                        assert err.max(initial=0) <= 8 * OC.eps_of(dt), (dt, a, n, kind, back, float(err.max()))
+
+
+def test_softmax_model_and_inputs_at_the_edges():
+    smallest = np.inf
+    for dt in OC.DTYPES:
+        name = np.dtype(dt).name
+        for K in OC.SOFTMAX_K:
+            rows = OC.softmax_rows(K)
+            assert rows[0] == 1 and rows[-1] == 3 * (256 // OP.softmax_group(K)) + 1
+            for r in rows:
+                x, g = OC.softmax_input(K, r, name)
+                want = OC.softmax_reference(x)
+                smallest = min(smallest, float(want.min()))
+                y = OP.softmax(x)
+                # every entry counts: none is excluded, none is sub-normal even in float32
+                assert (want > OC.TINY32).all() and np.isfinite(want).all()
+                assert OC.softmax_ratio(y, x, want) <= 1 and OC.row_sum_ratio(y) <= 1, (name, K, r)
+                if r > 1 and K > 1:          # K = 1 is 1.0 whatever is read
+                    assert not np.array_equal(y[0], y[1])
+                back = OP.softmax_backprop(y, g)
+                assert OC.softmax_backprop_ratio(back, y, g, OC.softmax_backprop_reference(y, g, 1.0), 1.0) <= 1, (name, K, r)
+        for K in OC.SPECIAL_K:
+            x, g = OC.special_rows(K, name)
+            with np.errstate(invalid='ignore'):
+                y = OP.softmax(x)
+            want = OC.softmax_reference(x)
+            row = dict(zip(OC.SPECIAL_ROWS, y))
+            assert np.all(row['equal'] == dt(1) / dt(K)) or K & (K - 1)
+            assert np.allclose(row['equal'], 1 / K)
+            assert row['saturated'][K // 2] == 1 or dt == np.float64
+            assert np.array_equal(row['some -inf'] == 0, np.isneginf(x[2])) and np.isnan(row['all -inf']).all()
+            assert set(np.unique(row['+-1e4'])) == {0, dt(1) / dt((K + 1) // 2)}
+            assert np.array_equal(np.isnan(y), np.isnan(want)) and OC.softmax_ratio(y, x, want) <= 1
+            back = OP.softmax_backprop(y, g)
+            ratio = OC.softmax_backprop_ratio(back, y, g, OC.softmax_backprop_reference(y, g, 1.0), 1.0)
+            assert ratio <= 1 and np.all(back[y == 0] == 0) and np.isnan(back[3]).all()
+            # the reference's own expression cancels on the saturated row: the bound tells the two forms apart
+            naive = OC.softmax_backprop_ratio(OC.softmax_backprop_naive(y[1:2], g[1:2], 1.0), y[1:2], g[1:2],
+                                              OC.softmax_backprop_reference(y[1:2], g[1:2], 1.0), 1.0)
+            print(f'softmax backprop model {name} K={K}: ratio {ratio:.2e}, the reference\'s expression on the saturated row {naive:.2e}')
+            assert naive > 1 or dt == np.float64       # it misses the bound the kernel's form meets
+        for K in OC.GUMBEL_K:
+            x, u, g, eps = OC.gumbel_input(K, name)
+            assert (u == 0).any(axis=1).all() and (u == np.nextafter(dt(1), dt(0))).any(axis=1).all() and (u < 1).all() and eps > 0
+            for tau in OC.GUMBEL_TAU:
+                y = OP.softmax(x, u, tau, eps)
+                extra, logits = OC.gumbel_extra(x, u, tau, eps)
+                assert np.isfinite(logits).all() and np.isfinite(y).all()
+                assert OC.softmax_ratio(y, logits, OC.softmax_reference(logits), extra) <= 1
+    assert smallest > OC.TINY32
+    print(f'softmax inputs: the smallest probability of any case is {smallest:.2e} (float32 tiny {OC.TINY32:.2e})')
