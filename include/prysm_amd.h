@@ -1212,6 +1212,44 @@ int pm_ifg_combine(int32_t dtype, int32_t typ, int32_t complex_out, int64_t rows
 /* PM_IFG_PSD_ABC: a / (1 + (nu / b)^c); PM_IFG_PSD_AB: a nu^(-b) (interferogram.py:289-330), n values.  One launch. */
 int pm_ifg_psd_model(int32_t dtype, int32_t kind, int64_t n, const void* nu, double a, double b, double c, void* out, void* stream);
 
+/* --- surfaces synthesised from a PSD (csrc/psdsynth.hip) ------------------------------------ */
+/* The pointwise passes of synthesize_surface_from_psd and render_synthetic_surface (prysm/interferogram.py:333-432) around the two
+ * transforms of pm_fft2, on a stack of `batch` (<= 65535) surfaces of rows x cols samples of the real type `dtype` (PM_F32 / PM_F64;
+ * spectra and fields are complex of the same precision), rows `ld` and members `bstride` elements apart.  prysm_amd/psdsynth_plan.py
+ * is the same arithmetic in numpy. */
+enum { PM_PSD_MASK_NONE = 0, PM_PSD_MASK_ARRAY = 1, PM_PSD_MASK_CIRCLE = 2 };
+
+/* a PSD evaluated inside pm_psd_signal: kind PM_IFG_PSD_ABC a / (1 + (nu / b)^c) or PM_IFG_PSD_AB a nu^(-b) at nu = the root sum of
+ * squares of element (row, col) of forward_ft_unit(dxg, rows) and forward_ft_unit(dxg, cols), each with its centre sample n / 2
+ * replaced by a tenth of the next one (interferogram.py:404-412), in double, rounded once to the data's type */
+typedef struct pm_psd_model {
+    int32_t kind, reserved;
+    double a, b, c, dxg;
+} pm_psd_model;
+
+/* np.random.rand (interferogram.py:347) on the device: uniform numbers in [0, 1) from Philox4x32-10 with key = seed and counter =
+ * (pixel low word, pixel high word, surface0 + member, 0), pixel = row * cols + col.  PM_F32: (word 0 >> 8) 2^-24; PM_F64:
+ * ((word 0 >> 5) 2^26 + (word 1 >> 6)) 2^-53; every step exact.  One launch. */
+int pm_psd_uniform(int32_t dtype, int64_t batch, int64_t rows, int64_t cols, int64_t seed, int64_t surface0, void* out, int64_t ld,
+                   int64_t bstride, void* stream);
+/* exp(i angle(X)) sqrt(A psd) (interferogram.py:349, 363) in place on the complex spectrum X: (X / |X|, or 1 where X == 0) times
+ * sqrt(area psd) in the data's type; a negative psd gives NaN.  Exactly one of `psd` (a real rows x cols array shared by the stack,
+ * rows psd_ld apart) and `model` is given.  One launch. */
+int pm_psd_signal(int32_t dtype, int64_t batch, int64_t rows, int64_t cols, void* spectrum, int64_t ld, int64_t bstride, const void* psd,
+                  int64_t psd_ld, const pm_psd_model* model, double area, void* stream);
+/* out = real(field) (interferogram.py:367), NaN where the mask fails (interferogram.py:418-424): PM_PSD_MASK_ARRAY a rows x cols array
+ * of bytes shared by the stack (0: outside), PM_PSD_MASK_CIRCLE hypot(x, y) <= radius on make_xy_grid's x = T(col - cols / 2) T(step),
+ * y = T(row - rows / 2) T(step); and sums[2 b], sums[2 b + 1] = the count and the sum of squares of the finite pixels of member b,
+ * as doubles, the same bits every run.  Two launches. */
+size_t pm_psd_finish_workspace(int64_t batch, int64_t rows, int64_t cols);
+int pm_psd_finish(int32_t dtype, int32_t mask_kind, int64_t batch, int64_t rows, int64_t cols, const void* field, int64_t ld, int64_t bstride,
+                  const void* mask, int64_t mask_ld, double radius, double step, void* out, int64_t out_ld, int64_t out_bstride, void* sums,
+                  void* workspace, size_t workspace_bytes, void* stream);
+/* z *= rms / sqrt(sum / count) (interferogram.py:427-430) with the sums of pm_psd_finish read on the device; a member with count 0 or
+ * sum 0 is left as it is.  One launch. */
+int pm_psd_scale(int32_t dtype, int64_t batch, int64_t rows, int64_t cols, void* z, int64_t ld, int64_t bstride, const void* sums, double rms,
+                 void* stream);
+
 /* --- masked modal fitting (csrc/modalfit.hip) ---------------------------------------------- */
 /* lstsq, normalize_modes and orthogonalize_modes of prysm/polynomials/fitting.py:103-187 over a stored basis: K real planes
  * modes[k * mode_stride + p], p < npts, PM_F32 or PM_F64, K <= PM_MODES_FIT_MAX (more: PM_ERR_UNSUPPORTED).  A point is valid when

@@ -65,6 +65,7 @@ PM_IFG_WIN_WELCH, PM_IFG_WIN_HANN, PM_IFG_WIN_ARRAY = 0, 1, 2
 PM_IFG_LP, PM_IFG_HP, PM_IFG_BP, PM_IFG_BR = 0, 1, 2, 3
 PM_IFG_PSD_ABC, PM_IFG_PSD_AB = 0, 1
 PM_IFG_IIR_HANN, PM_IFG_IIR_LPF = 1, 2
+PM_PSD_MASK_NONE, PM_PSD_MASK_ARRAY, PM_PSD_MASK_CIRCLE = 0, 1, 2
 PM_MODES_FIT_MAX = 128
 PM_MODES_REC_COUNT, PM_MODES_REC_RANK, PM_MODES_REC_G = 0, 1, 2
 PM_MODES_GRAM, PM_MODES_RHS = 1, 2
@@ -117,6 +118,10 @@ class pm_lenslets(ctypes.Structure):
 class pm_ifg_coords(ctypes.Structure):
     _fields_ = [('mode', c_i32), ('linspace', c_i32), ('x', c_vp), ('y', c_vp), ('ldx', c_i64), ('ldy', c_i64), ('ox', c_i64), ('oy', c_i64),
                 ('dx', c_f64), ('dy', c_f64), ('x0', c_f64), ('y0', c_f64)]
+
+
+class pm_psd_model(ctypes.Structure):
+    _fields_ = [('kind', c_i32), ('reserved', c_i32), ('a', c_f64), ('b', c_f64), ('c', c_f64), ('dxg', c_f64)]
 
 
 # name -> (restype, argtypes); tests/test_capi_symbols.py checks this table against include/prysm_amd.h
@@ -269,6 +274,11 @@ SIGNATURES = {
     'pm_ifg_iir': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_f64, c_f64, c_f64, c_f64, c_vp, c_vp, c_i64, c_vp]),
     'pm_ifg_combine': (c_i32, [c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     'pm_ifg_psd_model': (c_i32, [c_i32, c_i32, c_i64, c_vp, c_f64, c_f64, c_f64, c_vp, c_vp]),
+    'pm_psd_uniform': (c_i32, [c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp]),
+    'pm_psd_signal': (c_i32, [c_i32, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, ctypes.POINTER(pm_psd_model), c_f64, c_vp]),
+    'pm_psd_finish_workspace': (c_sz, [c_i64, c_i64, c_i64]),
+    'pm_psd_finish': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_f64, c_f64, c_vp, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    'pm_psd_scale': (c_i32, [c_i32, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_f64, c_vp]),
     'pm_modes_record_doubles': (c_sz, [c_i64, c_i64]),
     'pm_modes_gram_workspace': (c_sz, [c_i32, c_i64, c_i64, c_i64]),
     'pm_modes_gram': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_sz, c_vp]),

@@ -1369,3 +1369,79 @@ def ifg_psd_model(kind, nu, a, b, c=0.0):
     out = torch.empty_like(nu)
     L.check(L.load().pm_ifg_psd_model(_rcode(nu.dtype), int(kind), nu.numel(), L.ptr(nu), float(a), float(b), float(c), L.ptr(out), L.stream_ptr()))
     return out
+
+
+# --------------------------------------------------------------------------- surfaces synthesised from a PSD (csrc/psdsynth.hip)
+
+def _stack3(t):
+    """a real or complex (B, m, n) device tensor as the unit addresses it: unit column stride, rows and members that do not overlap"""
+    if t.dim() != 3 or not t.is_cuda:
+        raise TypeError('a (batch, rows, cols) device tensor is required')
+    B, m, n = t.shape
+    if t.numel() and (t.stride(2) != 1 or (m > 1 and t.stride(1) < n) or (B > 1 and t.stride(0) < m * (t.stride(1) if m > 1 else n))):
+        raise ValueError('the rows of a surface must be contiguous, and rows and surfaces must not overlap')
+    return t, (t.stride(1) if m > 1 else n), (t.stride(0) if B > 1 else m * (t.stride(1) if m > 1 else n))
+
+
+def psd_uniform(shape, dtype, seed, surface0=0, out=None):
+    """pm_psd_uniform: a (B, m, n) tensor of uniform numbers in [0, 1), surface b drawn with surface index surface0 + b"""
+    B, m, n = (int(v) for v in shape)
+    if out is None:
+        out = torch.empty((B, m, n), dtype=dtype, device=L.device())
+    out, ld, bs = _stack3(out)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    L.check(L.load().pm_psd_uniform(_rcode(dtype), B, m, n, seed - (1 << 64) if seed >> 63 else seed, int(surface0), L.ptr(out), ld, bs, L.stream_ptr()))
+    return out
+
+
+def psd_signal(spectrum, area, *, psd=None, model=None):
+    """pm_psd_signal in place on a complex (B, m, n) spectrum: psd a real (m, n) array, or model = (kind, a, b, c, dxg)"""
+    spectrum, ld, bs = _stack3(spectrum)
+    B, m, n = spectrum.shape
+    rdt = L._REAL_OF[spectrum.dtype]
+    pld, rec = 0, None
+    if psd is not None:
+        psd, pld = _rows(psd, rdt)
+        if tuple(psd.shape) != (m, n):
+            raise ValueError(f'the psd has shape {tuple(psd.shape)}, the spectrum {(m, n)}')
+    if model is not None:
+        rec = L.pm_psd_model(int(model[0]), 0, float(model[1]), float(model[2]), float(model[3]), float(model[4]))
+    L.check(L.load().pm_psd_signal(_rcode(rdt), B, m, n, L.ptr(spectrum), ld, bs, L.ptr(psd), pld, ctypes.byref(rec) if rec is not None else None,
+                                   float(area), L.stream_ptr()))
+    return spectrum
+
+
+def psd_finish(field, *, mask=None, circle=None, out=None):
+    """pm_psd_finish: (z = real(field) with NaN outside the mask, the (B, 2) float64 device tensor of counts and sums of squares).
+    mask: a bool / uint8 (m, n) device tensor; circle: (radius, step)"""
+    lib = L.load()
+    field, ld, bs = _stack3(field)
+    B, m, n = field.shape
+    rdt = L._REAL_OF[field.dtype]
+    if out is None:
+        out = torch.empty((B, m, n), dtype=rdt, device=field.device)
+    out, old, obs = _stack3(out)
+    if tuple(out.shape) != (B, m, n) or out.dtype != rdt:
+        raise ValueError('the output differs from the field in shape or precision')
+    kind, mld, radius, step = L.PM_PSD_MASK_NONE, 0, 0.0, 0.0
+    if mask is not None:
+        if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (m, n):
+            raise ValueError(f'the mask must be a bool or uint8 array of shape {(m, n)}')
+        mask = _rows2d(mask)
+        kind, mld = L.PM_PSD_MASK_ARRAY, _ld(mask)
+    elif circle is not None:
+        kind, radius, step = L.PM_PSD_MASK_CIRCLE, float(circle[0]), float(circle[1])
+    sums = torch.empty((B, 2), dtype=torch.float64, device=field.device)
+    nbytes = lib.pm_psd_finish_workspace(B, m, n)
+    ws = L.workspace(nbytes)
+    L.check(lib.pm_psd_finish(_rcode(rdt), kind, B, m, n, L.ptr(field), ld, bs, L.ptr(mask), mld, radius, step, L.ptr(out), old, obs, L.ptr(sums),
+                              L.ptr(ws), nbytes, L.stream_ptr()))
+    return out, sums
+
+
+def psd_scale(z, sums, rms):
+    """pm_psd_scale in place: each surface times rms / sqrt(sum / count), the sums read on the device"""
+    z, ld, bs = _stack3(z)
+    B, m, n = z.shape
+    L.check(L.load().pm_psd_scale(_rcode(z.dtype), B, m, n, L.ptr(z), ld, bs, L.ptr(sums), float(rms), L.stream_ptr()))
+    return z

@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "pm_entry.h"
+#include "pm_philox.h"      // Words, philox4x32, uniform53
 
 namespace pm {
 namespace {
@@ -37,26 +38,6 @@ __constant__ double kLogFact[kLogFactN] = {
     25.191221182738683, 27.89927138384089, 30.671860106080672, 33.50507345013689, 36.39544520803305, 39.339884187199495,
     42.335616460753485, 45.38013889847691, 48.47118135183522, 51.60667556776438, 54.78472939811232, 58.00360522298052,
     61.26170176100201, 64.55753862700634, 67.88974313718153, 71.257038967168, 74.65823634883017, 78.0922235533153};
-
-struct Words {
-    uint32_t w[4];
-};
-
-__device__ __forceinline__ Words philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = uint64_t(0xD2511F53u) * c0, p1 = uint64_t(0xCD9E8D57u) * c2;
-        const uint32_t n0 = uint32_t(p1 >> 32) ^ c1 ^ k0, n2 = uint32_t(p0 >> 32) ^ c3 ^ k1;
-        c1 = uint32_t(p1), c3 = uint32_t(p0), c0 = n0, c2 = n2;
-        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-    }
-    return Words{{c0, c1, c2, c3}};
-}
-
-// two words -> [0, 1) with 53 random bits, every step exact
-__device__ __forceinline__ double uniform53(uint32_t hi, uint32_t lo) {
-    return (double(hi >> 5) * 67108864.0 + double(lo >> 6)) * 0x1p-53;
-}
 
 // the stream of one sample: key = seed, counter = (pixel, global frame, block)
 struct Stream {

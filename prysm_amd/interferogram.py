@@ -20,6 +20,15 @@ reads per public call:
   slope                 1 launch
   pvr                   the 37 fringe Zernike planes (1 launch), polynomials.lstsq (4 launches), the projection from coefficients that
                         stay on the device (pm_zernike_sum, 1 launch), pv and rms (4 launches and 1 host read each): 2 host reads
+  render_synthetic_surface    with abc_psd / ab_psd, a seed, 'circle' and rms: 5 launches of csrc/psdsynth.hip (uniform numbers, the
+                        signal in place on their spectrum, the real part with the mask and the partial sums, their fold, the scale)
+                        and the two transforms' own launches; no host read.  Stored: the random numbers, their spectrum, the inverse
+                        transform's complex output and z -- no nu_r, psd, phase or mask map.  An array mask is read in the third
+                        launch; another callable costs 3 more launches (the frequencies, nu_r, the callable's own) and a psd array
+  synthesize_surface_from_psd    4 launches of the unit (3 with randnums) and the transforms; 1 host read of nu_y[0] when nu_y is on
+                        the device
+  fit_psd               1 host read of f and psd, then numpy (and scipy.optimize.least_squares but for ab_psd)
+  make_random_subaperture_mask    a slice assignment
 
 Coordinates.  The object keeps x and y as (origin index, step) and hands that to the kernels, which generate the coordinates; .x, .y,
 .r and .t materialise arrays on demand (make_xy_grid, cart_to_polar).  As in the reference, coordinates that were never looked at are
@@ -29,10 +38,17 @@ latcal or pad, are carried through crop.  Assigning .x or .y switches the object
 Reference behaviour that is kept: the statistics and crop use isfinite (+-inf is left out), dropout_percentage and fill use isnan;
 fit_plane fits {x, y} without a piston term; fit_sphere fits {rho^2, 1} on linspace(-1, 1, n) grids and only its rho^2 term is removed;
 spike_clip compares |data|, not |data - mean|, with nsigma std; bandlimited_rms takes the spacing from two samples along axis 0 and uses
-it for both axes; filter transforms unshifted data and returns the real part.
+it for both axes; filter transforms unshifted data and returns the real part; synthesize_surface_from_psd multiplies the UNSHIFTED
+spectrum's phase with the centred psd element by element, takes dx = dy = -1 / (2 nu_y[0]) whatever the parity of the lengths, and
+returns the real part of a complex inverse transform (the signal is Hermitian only on even lengths with a symmetric psd, so no
+half-spectrum inverse is used); render_synthetic_surface spaces the grid by size / (samples - 1) but masks on make_xy_grid(samples,
+diameter=size), and replaces the centre frequency by a tenth of the next one.
 
-Not here: fit_psd, synthesize_surface_from_psd and render_synthetic_surface,
-make_random_subaperture_mask, the Zygo readers and writers and save_*, the interferogram() fringe picture and all plotting.
+Random numbers.  The device generator is Philox4x32-10 keyed by `seed` (csrc/psdsynth.hip); without a seed one is drawn from Python's
+random, so random.seed() makes a session reproducible.  randnums= replaces the generator (the reference's np.random.rand values, for
+parity).  batch=B or a (B, m, n) randnums gives a stack, surface b drawn with surface index b and scaled to rms on its own.
+
+Not here: the Zygo readers and writers and save_*, the interferogram() fringe picture and all plotting.
 """
 import math
 
@@ -42,6 +58,7 @@ import torch
 from . import _lib as L
 from . import _ops
 from . import interferogram_plan as IP
+from . import psdsynth_plan as PP
 from ._richdata import RichData
 from .conf import config
 from .coordinates import broadcast_1d_to_2d, cart_to_polar, make_xy_grid
@@ -51,7 +68,8 @@ from .util import Sa, as_map, mean, pv, record, rms, std  # noqa: F401
 HeNe = 0.6328
 
 __all__ = ['HeNe', 'fit_plane', 'fit_sphere', 'make_window', 'window_2d_welch', 'hann2d', 'psd', 'bandlimited_rms', 'abc_psd', 'ab_psd',
-           'ideal_lpf_iir2d', 'designfilt2d', 'Interferogram', 'mean', 'rms', 'pv', 'Sa', 'std']
+           'ideal_lpf_iir2d', 'designfilt2d', 'Interferogram', 'mean', 'rms', 'pv', 'Sa', 'std', 'synthesize_surface_from_psd',
+           'render_synthetic_surface', 'fit_psd', 'make_random_subaperture_mask']
 
 _TILT = L.PM_IFG_TERM_X | L.PM_IFG_TERM_Y
 _POWER = L.PM_IFG_TERM_R2 | L.PM_IFG_TERM_PISTON
@@ -181,6 +199,110 @@ def ab_psd(nu, a, b):
     if not hasattr(nu, 'shape') or not tuple(np.shape(nu)):
         return a * nu ** (-b)
     return _ops.ifg_psd_model(L.PM_IFG_PSD_AB, _real(nu), a, b)
+
+
+def _forward_spectrum(u):
+    """fft2 of the real stack u with PM_EPI_NONE, on the route PP.route names (the routes of _psd)"""
+    shape = tuple(u.shape[-2:])
+    way = PP.route(shape, stacked=u.shape[0] > 1)
+    if way == 'hermitian':
+        try:
+            return _ops.fft2(u, direction=-1, scale=1.0)
+        except NotImplementedError:      # a power of two outside the Hermitian path (a very small or very long row)
+            way = PP.route((0, shape[1]), stacked=u.shape[0] > 1)
+    if way == 'real_pairs' and _ops.real_pairs_ok(u[0]):
+        return _ops.fft2_real(u[0]).unsqueeze(0)
+    return _ops.fft2(u, direction=-1, scale=1.0)
+
+
+def _synthesize(shape, dtype, nu_y0, *, psd=None, model=None, randnums=None, seed=None, batch=None, mask=None, circle=None, rms=None):
+    """(dx, z): the chain of synthesize_surface_from_psd on a stack, with render_synthetic_surface's mask and scale in its last passes"""
+    lead = PP.check_random(shape, None if randnums is None else tuple(np.shape(randnums)), seed, batch)
+    dx, area, scale = PP.window(nu_y0, shape)
+    if randnums is not None:
+        u = L.as_device(randnums, dtype)
+        u = u if u.dim() == 3 else u.unsqueeze(0)
+    else:
+        u = _ops.psd_uniform((lead or 1,) + tuple(shape), dtype, PP.draw_seed() if seed is None else seed)
+    spectrum = _forward_spectrum(u)
+    _ops.psd_signal(spectrum, area, psd=psd, model=model)
+    shift = PP.shifts(shape)
+    field = _ops.fft2(spectrum, direction=1, scale=scale, in_shift=shift, out_shift=shift)
+    z, sums = _ops.psd_finish(field, mask=mask, circle=circle)
+    if rms is not None:
+        _ops.psd_scale(z, sums, rms)
+    return dx, (z if lead is not None else z[0])
+
+
+def _axes(shape, dx, dtype):
+    dev = L.device()
+    return torch.arange(shape[1], dtype=dtype, device=dev) * dx, torch.arange(shape[0], dtype=dtype, device=dev) * dx
+
+
+def synthesize_surface_from_psd(psd, nu_x, nu_y, *, randnums=None, seed=None):
+    """(x, y, z): a surface with the given 2-D PSD and a random phase (interferogram.py:333-368).  randnums, (m, n) or (B, m, n),
+    replaces the device generator, which seed keys; z takes the leading dimension of randnums."""
+    if randnums is not None and seed is not None:
+        raise ValueError('randnums replaces the generator: give randnums or seed, not both')
+    PP.check_shape(tuple(np.shape(psd)))
+    psd = _real(psd)
+    shape = tuple(psd.shape)
+    dx, z = _synthesize(shape, psd.dtype, float(nu_y[0]), psd=psd, randnums=randnums, seed=seed)
+    x, y = _axes(shape, dx, psd.dtype)
+    return x, y, z
+
+
+def render_synthetic_surface(size, samples, rms=None, mask=None, psd_fcn=abc_psd, *, seed=None, randnums=None, batch=None, **psd_fcn_kwargs):
+    """(x, y, z): a synthetic surface of `samples` x `samples` points over `size`, from a PSD function, NaN outside the mask (None, an
+    array, or 'circle'), scaled to `rms` if given (interferogram.py:371-432).  abc_psd and ab_psd are evaluated inside the signal kernel;
+    any other callable is called with the radial frequencies as a device tensor.  batch=B: z is (B, samples, samples), each surface
+    scaled on its own."""
+    PP.check_mask_name(mask)
+    samples = PP.check_samples(samples)
+    shape, dtype = (samples, samples), _rdtype()
+    PP.check_random(shape, None if randnums is None else tuple(np.shape(randnums)), seed, batch)
+    dxg = size / (samples - 1)
+    nu = PP.freq_vector(samples, dxg)
+    source = {}
+    if psd_fcn is abc_psd or psd_fcn is ab_psd:
+        source['model'] = PP.model_record(PP.ABC if psd_fcn is abc_psd else PP.AB, psd_fcn_kwargs) + (dxg,)
+    else:
+        nu_r, _ = cart_to_polar(L.as_device(nu, dtype), L.as_device(nu, dtype))
+        source['psd'] = _real(psd_fcn(nu_r, **psd_fcn_kwargs))
+        if tuple(source['psd'].shape) != shape:
+            raise ValueError(f"the PSD function returned shape {tuple(source['psd'].shape)} for frequencies of shape {shape}")
+    if isinstance(mask, str):
+        source['circle'] = (size / 2, size / samples)      # make_xy_grid(samples, diameter=size): the step is size / samples
+    elif mask is not None:
+        m = mask if isinstance(mask, torch.Tensor) else L.as_device(np.asarray(mask))
+        if tuple(m.shape) != shape:
+            raise ValueError(f'the mask has shape {tuple(m.shape)}, the surface {shape}')
+        source['mask'] = L.as_device(m if m.dtype in (torch.bool, torch.uint8) else m != 0)
+    dx, z = _synthesize(shape, dtype, nu[0], randnums=randnums, seed=seed, batch=batch, rms=rms, **source)
+    x, y = _axes(shape, dx, dtype)
+    return x, y, z
+
+
+def fit_psd(f, psd, callable=abc_psd, guess=None, return_='coefficients'):      # noqa: A002 -- the reference's name
+    """Fit the parameters of a PSD model to a 1-D curve in log10 space (interferogram.py:435-544): ab_psd in closed form after dropping
+    the first five samples (no scipy needed), abc_psd from a seed taken from the data with bounds (0, inf), any other callable
+    unbounded from `guess` or [100, 1, ...].  f and psd are read back once; the fit runs on the host."""
+    host = [v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v) for v in (f, psd)]
+    if callable is abc_psd:
+        return PP.fit_psd(host[0], host[1], PP.abc, PP.ABC, guess, return_)
+    if callable is ab_psd:
+        return PP.fit_psd(host[0], host[1], PP.ab, PP.AB, guess, return_)
+    return PP.fit_psd(host[0], host[1], callable, None, guess, return_)
+
+
+def make_random_subaperture_mask(shape, mask):
+    """A bool array of `shape` that holds `mask` at a random offset and False elsewhere (interferogram.py:635-665)."""
+    shape = tuple(int(s) for s in shape)
+    dy, dx = PP.subaperture_offsets(shape, tuple(np.shape(mask)))      # a mask that does not fit is refused before the device is touched
+    m = L.as_device(mask if isinstance(mask, torch.Tensor) else np.asarray(mask))
+    out = torch.zeros(shape, dtype=torch.bool, device=L.device())
+    out[dy:dy + m.shape[0], dx:dx + m.shape[1]] = m != 0
+    return out
 
 
 def hann2d(M, N):
@@ -507,6 +629,17 @@ class Interferogram(RichData):
         dx = self.dx
         gx, gy, gr = _ops.ifg_slope(self.data, dx)
         return RichData(gx, dx, None), RichData(gy, dx, None), RichData(gr, dx, None)
+
+    @staticmethod
+    def render_from_psd(size, samples, rms=None, mask='circle', psd_fcn=abc_psd, **kw):
+        """An Interferogram of a synthetic surface (interferogram.py:1191-1225): render_synthetic_surface with the circular mask by
+        default, dx the spacing of its x axis, the HeNe wavelength.  seed= and randnums= are passed on."""
+        x, _, z = render_synthetic_surface(size, samples, rms=rms, mask=mask, psd_fcn=psd_fcn, **kw)
+        if z.dim() != 2:
+            raise ValueError('an Interferogram holds one surface: render a stack with render_synthetic_surface')
+        samples = PP.check_samples(samples)
+        dx = PP.window(PP.freq_vector(samples, size / (samples - 1))[0], (samples, samples))[0]      # x[1] - x[0] without a host read
+        return Interferogram(phase=z, dx=dx, wavelength=HeNe)
 
     def copy(self):
         out = Interferogram(self.data.clone(), self.dx, self.wavelength, self.intensity, self.meta)
