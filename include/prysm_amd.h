@@ -1250,6 +1250,72 @@ int pm_psd_finish(int32_t dtype, int32_t mask_kind, int64_t batch, int64_t rows,
 int pm_psd_scale(int32_t dtype, int64_t batch, int64_t rows, int64_t cols, void* z, int64_t ld, int64_t bstride, const void* sums, double rms,
                  void* stream);
 
+/* --- Jones and Mueller calculus (csrc/jones.hip) -------------------------------------------- */
+/* prysm/x/polarization.py:45-475 and 555-578 per pixel of a rows x cols grid, `dtype` PM_C64 or PM_C128, arithmetic in its real type.
+ * A Jones field has four complex components per pixel in the order (0,0), (0,1), (1,0), (1,1), a Jones vector two, (0,0), (1,0).
+ * PM_JONES_AOS: the reference's (..., 2, 2) / (..., 2, 1), pixel (r, c) at (r ld + c) ncomp elements.  PM_JONES_PLANES: (ncomp, rows,
+ * cols), component k of pixel (r, c) at k pstride + r ld + c elements (pstride >= rows ld; ignored for aos).  ld counts pixels and is
+ * at least cols.  Every entry point is one launch, reads each input once and stores each output once; an empty shape returns 0.
+ * prysm_amd/x/polarization_plan.py is the same arithmetic in numpy. */
+enum { PM_JONES_AOS = 0, PM_JONES_PLANES = 1 };
+enum { PM_JONES_ROTATION = 0, PM_JONES_RETARDER = 1, PM_JONES_DIATTENUATOR = 2, PM_JONES_VORTEX = 3, PM_JONES_LINPOL_VECTOR = 4 };
+enum { PM_JONES_FIELD_NONE = 0, PM_JONES_FIELD_REAL = 1, PM_JONES_FIELD_COMPLEX = 2 };
+#define PM_JONES_LEAKAGE_IDENTITY 1
+#define PM_JONES_MAX_CHAIN 6
+
+/* a real parameter: `map` (rows x cols of the dtype's real type, rows ld apart) where it is not NULL, else the host's `value` */
+typedef struct pm_jones_param {
+    double value;
+    const void* map;
+    int64_t ld;
+} pm_jones_param;
+
+/* kind and parameters of a generated optic, angles in radians:
+ *   PM_JONES_ROTATION       p[0] = theta                         jones_rotation_matrix (polarization.py:133-160)
+ *   PM_JONES_RETARDER       p[0] = retardance, p[1] = theta      linear_retarder, the wave plates (:163-196, 234-272)
+ *   PM_JONES_DIATTENUATOR   p[0] = alpha, p[1] = theta           linear_diattenuator, linear_polarizer (:199-231, 275-293)
+ *   PM_JONES_VORTEX         p[0] = theta, p[1] = retardance, p[2] = rotate, charge; flags PM_JONES_LEAKAGE_IDENTITY puts the
+ *                           -i cos(retardance / 2) term on both diagonal elements (Mawet 2009 eq. 7), 0 on element (0,0) only as the
+ *                           reference does (:296-346).  charge x theta is formed in the map's precision before the cosine and sine
+ *   PM_JONES_LINPOL_VECTOR  p[0] = angle, multiplied by `charge` (1 for radians, pi / 180 for degrees) in the map's precision;
+ *                           the output is a vector                linear_pol_vector (:45-77) */
+typedef struct pm_jones_optic_desc {
+    int32_t kind, flags;
+    double charge;
+    pm_jones_param p[3];
+} pm_jones_optic_desc;
+
+/* one operand of pm_jones_chain: `map` in the chain's layout where it is not NULL, else the constant c = (re, im) of the four
+ * components (of the two of a vector in c[0..3]) */
+typedef struct pm_jones_operand {
+    const void* map;
+    int64_t ld, pstride;
+    double c[8];
+} pm_jones_operand;
+
+/* The optic of `optic` at every pixel, times the complex map `field` (rows field_ld apart) where it is not NULL: the generators
+ * followed by apply_polarization_optic (polarization.py:555-578) without the unit-amplitude optic in memory. */
+int pm_jones_optic(int32_t dtype, const pm_jones_optic_desc* optic, int64_t rows, int64_t cols, const void* field, int64_t field_ld, void* out,
+                   int32_t out_layout, int64_t out_ld, int64_t out_pstride, void* stream);
+/* out = A_1 @ A_2 @ ... @ A_count, 1 <= count <= PM_JONES_MAX_CHAIN, evaluated from the left as derot @ jones @ rot is
+ * (polarization.py:193-195, 228-230, 344).  vector_tail != 0: the last operand, and then the output, is a vector.  No temporary. */
+int pm_jones_chain(int32_t dtype, int32_t count, const pm_jones_operand* operands, int32_t layout, int32_t vector_tail, int64_t rows, int64_t cols,
+                   void* out, int32_t out_layout, int64_t out_ld, int64_t out_pstride, void* stream);
+/* out = field x in (polarization.py:573-576) for matrices (ncomp 4) or vectors (ncomp 2); field_kind PM_JONES_FIELD_COMPLEX a complex
+ * map, PM_JONES_FIELD_REAL a map of the real type, PM_JONES_FIELD_NONE the relayout alone (aos <-> planes, bit-exact).  out may be in
+ * when layouts and strides are equal; in == out with anything else is refused.  Arrays that overlap in part are NOT detected and
+ * give undefined results: the caller keeps in and out either identical or disjoint. */
+int pm_jones_scale(int32_t dtype, int32_t ncomp, int64_t rows, int64_t cols, const void* in, int32_t layout, int64_t ld, int64_t pstride,
+                   int32_t field_kind, const void* field, int64_t field_ld, void* out, int32_t out_layout, int64_t out_ld, int64_t out_pstride,
+                   void* stream);
+/* jones_to_mueller (polarization.py:349-407): the sixteen real elements of Re(U (J* (x) J) U^H) per pixel, row-major, as closed forms
+ * in the four components.  out holds the real type: aos 16 values per pixel, planes 16 planes. */
+int pm_jones_to_mueller(int32_t dtype, int64_t rows, int64_t cols, const void* jones, int32_t layout, int64_t ld, int64_t pstride, void* out,
+                        int32_t out_layout, int64_t out_ld, int64_t out_pstride, void* stream);
+/* pauli_coefficients (polarization.py:455-475): the four complex planes c0 ... c3 of out, out_pstride apart. */
+int pm_pauli_coefficients(int32_t dtype, int64_t rows, int64_t cols, const void* jones, int32_t layout, int64_t ld, int64_t pstride, void* out,
+                          int64_t out_ld, int64_t out_pstride, void* stream);
+
 /* --- masked modal fitting (csrc/modalfit.hip) ---------------------------------------------- */
 /* lstsq, normalize_modes and orthogonalize_modes of prysm/polynomials/fitting.py:103-187 over a stored basis: K real planes
  * modes[k * mode_stride + p], p < npts, PM_F32 or PM_F64, K <= PM_MODES_FIT_MAX (more: PM_ERR_UNSUPPORTED).  A point is valid when

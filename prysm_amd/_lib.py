@@ -66,6 +66,10 @@ PM_IFG_LP, PM_IFG_HP, PM_IFG_BP, PM_IFG_BR = 0, 1, 2, 3
 PM_IFG_PSD_ABC, PM_IFG_PSD_AB = 0, 1
 PM_IFG_IIR_HANN, PM_IFG_IIR_LPF = 1, 2
 PM_PSD_MASK_NONE, PM_PSD_MASK_ARRAY, PM_PSD_MASK_CIRCLE = 0, 1, 2
+PM_JONES_AOS, PM_JONES_PLANES = 0, 1
+PM_JONES_ROTATION, PM_JONES_RETARDER, PM_JONES_DIATTENUATOR, PM_JONES_VORTEX, PM_JONES_LINPOL_VECTOR = range(5)
+PM_JONES_FIELD_NONE, PM_JONES_FIELD_REAL, PM_JONES_FIELD_COMPLEX = 0, 1, 2
+PM_JONES_LEAKAGE_IDENTITY, PM_JONES_MAX_CHAIN = 1, 6
 PM_MODES_FIT_MAX = 128
 PM_MODES_REC_COUNT, PM_MODES_REC_RANK, PM_MODES_REC_G = 0, 1, 2
 PM_MODES_GRAM, PM_MODES_RHS = 1, 2
@@ -122,6 +126,18 @@ class pm_ifg_coords(ctypes.Structure):
 
 class pm_psd_model(ctypes.Structure):
     _fields_ = [('kind', c_i32), ('reserved', c_i32), ('a', c_f64), ('b', c_f64), ('c', c_f64), ('dxg', c_f64)]
+
+
+class pm_jones_param(ctypes.Structure):
+    _fields_ = [('value', c_f64), ('map', c_vp), ('ld', c_i64)]
+
+
+class pm_jones_optic_desc(ctypes.Structure):
+    _fields_ = [('kind', c_i32), ('flags', c_i32), ('charge', c_f64), ('p', pm_jones_param * 3)]
+
+
+class pm_jones_operand(ctypes.Structure):
+    _fields_ = [('map', c_vp), ('ld', c_i64), ('pstride', c_i64), ('c', c_f64 * 8)]
 
 
 # name -> (restype, argtypes); tests/test_capi_symbols.py checks this table against include/prysm_amd.h
@@ -279,6 +295,11 @@ SIGNATURES = {
     'pm_psd_finish_workspace': (c_sz, [c_i64, c_i64, c_i64]),
     'pm_psd_finish': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_f64, c_f64, c_vp, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
     'pm_psd_scale': (c_i32, [c_i32, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_f64, c_vp]),
+    'pm_jones_optic': (c_i32, [c_i32, ctypes.POINTER(pm_jones_optic_desc), c_i64, c_i64, c_vp, c_i64, c_vp, c_i32, c_i64, c_i64, c_vp]),
+    'pm_jones_chain': (c_i32, [c_i32, c_i32, ctypes.POINTER(pm_jones_operand), c_i32, c_i32, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, c_vp]),
+    'pm_jones_scale': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_i32, c_i64, c_i64, c_vp]),
+    'pm_jones_to_mueller': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, c_vp]),
+    'pm_pauli_coefficients': (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp]),
     'pm_modes_record_doubles': (c_sz, [c_i64, c_i64]),
     'pm_modes_gram_workspace': (c_sz, [c_i32, c_i64, c_i64, c_i64]),
     'pm_modes_gram': (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_sz, c_vp]),

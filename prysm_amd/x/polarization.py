@@ -4,13 +4,47 @@ The reference's jones_adapter calls the wrapped propagation function four times,
 (..., 2, 2) Jones field.  The four elements are independent fields of one shape, i.e. a batch: here they go
 through the FFT routines as ONE (4, m, n) stack (one launch pair), and through the matrix-DFT executors
 element by element.
-"""
-import functools
 
+Jones and Mueller calculus (polarization.py:45-475, 555-578) -- the polarization vectors, the generated optics, products of Jones
+maps, the conversion to Mueller matrices and the Pauli coefficients -- runs on the kernels of csrc/jones.hip, one launch per call:
+every input is read once, every output stored once, nothing in between is kept in memory.  polarization_plan.py restates each kernel
+in numpy.
+
+Layouts.  ``layout='aos'`` is the reference's (..., 2, 2) / (..., 2, 1); ``layout='planes'`` is (4, ...) / (2, ...), the stack the
+FFT routines take as one launch pair, so a Jones field generated with ``out_layout='planes'`` goes to propagation.focus as it is.
+``out_layout=None`` keeps the input's layout; ``out=`` writes into an array of the caller's (a window of a wider array included);
+``field=`` on a generator multiplies by a scalar field (apply_polarization_optic inside the generator).  to_planes and from_planes
+convert, jones_product is the chain A_1 @ ... @ A_K in one launch.
+
+A single 2 x 2, or a generator with scalar parameters and no ``shape=``, is built on the host: a small tensor, no launch.  An
+operand of shape (2, 2), (2, 1) or (2,) is ALWAYS read as such a single matrix or vector, also with layout='planes': a planes
+vector map over a 1-D grid of one or two pixels has the same shape and must be given a leading grid dimension, (2, 1, n).  The one
+call that is two launches: apply_polarization_optic with a single 2 x 2 optic, which first stores the broadcast optic
+(pm_jones_chain) and then scales it (pm_jones_scale).
+
+Departures from the reference, each pinned in tests/test_polarization_host.py (what needs no device) or
+tests/test_gpu_polarization.py (circular_pol_vector(shape=), the wrapper leaving theta alone):
+  - theta may be a map in linear_retarder, linear_diattenuator and the wave plates (the reference: ValueError, could not broadcast);
+  - circular_pol_vector(shape=...) returns the (*shape, 2, 1) vectors it documents (the reference: IndexError for any shape);
+  - vector_vortex_retarder leaves the caller's theta alone (the reference multiplies it by the charge in place);
+  - vector_vortex_retarder keeps the reference's -i cos(retardance / 2) on element (0,0) only; identity_leakage=True puts it on both
+    diagonal elements (Mawet 2009 eq. 7);
+  - jones_to_mueller(broadcast=False) on a single 2 x 2 is the same closed form, on the host;
+  - linear_diattenuator raises ValueError for a scalar alpha outside [0, 1] (the reference: assert); a map is not inspected;
+  - broadcast_kron is kept for the reference's interface only and is a torch.einsum: jones_to_mueller does not form the array.
+"""
+import ctypes
+import functools
+import math
+
+import numpy as np
 import torch
 
 from .. import _lib as L
 from .. import propagation
+from ..conf import config
+from ..coordinates import _real_dtype
+from . import polarization_plan as PP
 
 supported_propagation_funcs = ['focus', 'unfocus', 'focus_dft', 'unfocus_dft', 'angular_spectrum']
 
@@ -49,3 +83,385 @@ def add_jones_propagation(funcs_to_change=supported_propagation_funcs):
             wrapped = jones_adapter(func)
             wrapped._jones = True
             setattr(propagation, name, wrapped)
+
+
+# --------------------------------------------------------------------------- Jones and Mueller calculus (csrc/jones.hip)
+def _config_cdtype():
+    return L.torch_dtype(config.precision_complex)
+
+
+def _is_map(p):
+    return hasattr(p, 'ndim') and p.ndim > 0
+
+
+def _jones_view(t, layout, ncomp=None):
+    """(rows, cols, ld, pstride, ncomp, pix) of a Jones (or, ncomp 16, Mueller) tensor as the kernels address it, or None where they
+    cannot: the components of an aos pixel contiguous, the columns a pixel apart, the leading dimensions collapsing to rows"""
+    shape, st = tuple(t.shape), t.stride()
+    if layout == PP.AOS:
+        if ncomp is None:
+            ncomp, pix = PP.ncomp_of(shape, layout)
+        else:
+            pix = shape[:-2]
+            if shape[-2:] != PP.tail_of(ncomp):
+                raise ValueError(f'expected an array ending in {PP.tail_of(ncomp)}, got shape {shape}')
+        tail = PP.tail_of(ncomp)
+        if st[-1] != 1 and tail[1] > 1 or st[-2] != tail[1]:
+            return None
+        w = PP.window(pix, st[:-2], ncomp)
+        return None if w is None else (*w, 0, ncomp, pix)
+    if ncomp is None:
+        ncomp, pix = PP.ncomp_of(shape, layout)
+    else:
+        pix = shape[1:]
+        if shape[0] != ncomp:
+            raise ValueError(f'expected {ncomp} planes, got shape {shape}')
+    w = PP.window(pix, st[1:], 1)
+    if w is None or st[0] < w[0] * w[2]:
+        return None
+    return (*w, st[0], ncomp, pix)
+
+
+def _jones_in(x, layout):
+    """a Jones input on the device, addressable, and its view"""
+    t = x if isinstance(x, torch.Tensor) and x.device == L.device() else L.as_device(x)
+    if t.is_conj() or t.is_neg():
+        t = t.resolve_conj().resolve_neg()
+    if not t.is_complex():
+        t = t.to(L._COMPLEX_OF.get(t.dtype, torch.complex128))
+    v = _jones_view(t, layout)
+    if v is None:
+        t = t.contiguous()
+        v = _jones_view(t, layout)
+    return t, v
+
+
+def _jones_out(out, pix, ncomp, layout, dtype):
+    """the output tensor (allocated, or the caller's `out` checked) and its view"""
+    shape = (*pix, *PP.tail_of(ncomp)) if layout == PP.AOS else (ncomp, *pix)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=L.device())
+    else:
+        if not (isinstance(out, torch.Tensor) and out.device == L.device()):
+            raise TypeError('out must be a tensor on the device')
+        if tuple(out.shape) != shape or out.dtype != dtype:
+            raise ValueError(f'out must have shape {shape} and dtype {dtype}, got {tuple(out.shape)} and {out.dtype}')
+    v = _jones_view(out, layout, ncomp)
+    if v is None:
+        raise ValueError('out cannot be addressed by the kernels: unit stride along a row, rows at least a row apart')
+    return out, v
+
+
+def _real_map(p, rdt, pix, what):
+    t = p if isinstance(p, torch.Tensor) and p.device == L.device() else L.as_device(p)
+    if t.dtype != rdt:
+        t = t.to(rdt)
+    if tuple(t.shape) != tuple(pix):
+        raise ValueError(f'{what} has shape {tuple(t.shape)}, the other maps {tuple(pix)}')
+    w = PP.window(pix, t.stride(), 1)
+    if w is None:
+        t = t.contiguous()
+        w = PP.window(pix, t.stride(), 1)
+    return t, w[2]
+
+
+def _field_map(field, dtype, pix, real_ok=False):
+    t = field if isinstance(field, torch.Tensor) and field.device == L.device() else L.as_device(field)
+    if t.is_conj() or t.is_neg():
+        t = t.resolve_conj().resolve_neg()
+    rdt = L._REAL_OF[dtype]
+    if not t.is_complex() and real_ok:
+        want, kind = rdt, PP.FIELD_REAL
+    else:
+        want, kind = dtype, PP.FIELD_COMPLEX
+    if t.dtype != want:
+        t = t.to(want)
+    if tuple(t.shape) != tuple(pix):
+        raise ValueError(f'the field has shape {tuple(t.shape)}, the Jones array {tuple(pix)} pixels')
+    w = PP.window(pix, t.stride(), 1)
+    if w is None:
+        t = t.contiguous()
+        w = PP.window(pix, t.stride(), 1)
+    return t, w[2], kind
+
+
+def _host_tensor(a, dtype):
+    return L.as_device(np.ascontiguousarray(a)).to(dtype)
+
+
+def _np_cdtype(dtype):
+    return np.complex64 if dtype == torch.complex64 else np.complex128
+
+
+def _generate(kind, params, names, shape, field, out_layout, out, charge=1.0, leak=False):
+    """one pm_jones_optic launch -- or, with scalar parameters, no shape, no field and no out, the host's 2 x 2"""
+    maps = [p for p in params if _is_map(p)]
+    lay = PP.layout_code(out_layout or 'aos')
+    if not maps and shape is None and field is None and out is None:
+        dtype = _config_cdtype()
+        a = PP.optic(kind, [float(p) for p in params], (), _np_cdtype(dtype), charge=charge, leak=leak)
+        return _host_tensor(a.reshape(2) if kind == PP.LINPOL_VECTOR else a, dtype)
+    if maps:
+        pix = tuple(maps[0].shape)
+        dtype = L._COMPLEX_OF[_real_dtype(*maps, what='the parameter maps')]
+        if shape is not None and tuple(shape) != pix:
+            raise ValueError(f'shape={tuple(shape)} does not match the parameter maps {pix}')
+    else:
+        dtype = _config_cdtype()
+        if shape is not None:
+            pix = tuple(shape)
+        elif field is not None:
+            pix = tuple(field.shape)
+        else:
+            pix = tuple(out.shape[:-2]) if lay == PP.AOS else tuple(out.shape[1:])
+    rdt = L._REAL_OF[dtype]
+    ncomp = 2 if kind == PP.LINPOL_VECTOR else 4
+    o, (rows, cols, old, ops, _, _) = _jones_out(out, pix, ncomp, lay, dtype)
+    desc = L.pm_jones_optic_desc()
+    desc.kind, desc.flags, desc.charge = kind, (PP.LEAKAGE_IDENTITY if leak else 0), float(charge)
+    keep = []
+    for i, (p, name) in enumerate(zip(params, names)):
+        if _is_map(p):
+            t, ld = _real_map(p, rdt, pix, name)
+            keep.append(t)
+            desc.p[i].map, desc.p[i].ld = t.data_ptr(), ld
+        else:
+            desc.p[i].value = float(p)
+    fptr, fld = None, 0
+    if field is not None:
+        f, fld, _ = _field_map(field, dtype, pix)
+        keep.append(f)
+        fptr = L.ptr(f)
+    L.check(L.load().pm_jones_optic(L._COMPLEX_CODE[dtype], ctypes.byref(desc), rows, cols, fptr, fld, L.ptr(o), lay, old, ops, L.stream_ptr()))
+    return o
+
+
+def linear_pol_vector(angle, degrees=True, *, field=None, out_layout=None, out=None):
+    """A linearly polarized Jones vector at `angle` to the horizontal axis (polarization.py:45-77): a scalar angle gives the host's
+    (2,) vector, a map of angles the (*angle.shape, 2, 1) vectors in one launch (the degrees are converted inside it)."""
+    factor = math.pi / 180 if degrees else 1.0
+    if not _is_map(angle) and field is None and out is None:
+        dtype = _config_cdtype()
+        return _host_tensor(PP.optic(PP.LINPOL_VECTOR, [float(angle)], (), _np_cdtype(dtype), charge=factor).reshape(2), dtype)
+    return _generate(PP.LINPOL_VECTOR, [angle], ['angle'], None, field, out_layout, out, charge=factor)
+
+
+def circular_pol_vector(handedness='left', shape=None, *, out_layout=None, out=None):
+    """A circularly polarized Jones vector (polarization.py:80-104), (1, +-i) / sqrt(2).  Departure: with shape= the reference raises
+    IndexError; here it returns the (*shape, 2, 1) vectors it documents, filled in one launch."""
+    if handedness not in ('left', 'right'):
+        raise ValueError(f"unknown handedness {handedness}, use 'left' or 'right'")
+    v = np.array([1 / np.sqrt(2), (1j if handedness == 'left' else -1j) / np.sqrt(2)], dtype=config.precision_complex)
+    if shape is None and out is None:
+        return _host_tensor(v, _config_cdtype())
+    return _product([v.reshape(2, 1)], 'aos', out_layout, out, pix=None if shape is None else tuple(shape), dtype=_config_cdtype())
+
+
+def jones_rotation_matrix(theta, shape=None, *, field=None, out_layout=None, out=None):
+    """The rotation matrix [[cos, sin], [-sin, cos]] of the coordinate system transverse to propagation (polarization.py:133-160);
+    theta a scalar or a map."""
+    return _generate(PP.ROTATION, [theta], ['theta'], shape, field, out_layout, out)
+
+
+def linear_retarder(retardance, theta=0, shape=None, *, field=None, out_layout=None, out=None):
+    """A homogeneous linear retarder rot(-theta) diag(1, exp(i retardance)) rot(theta) (polarization.py:163-196) in closed form.
+    Departure: theta may be a map as well as the retardance (the reference fails to broadcast there)."""
+    return _generate(PP.RETARDER, [retardance, theta], ['retardance', 'theta'], shape, field, out_layout, out)
+
+
+def linear_diattenuator(alpha, theta=0, shape=None, *, field=None, out_layout=None, out=None):
+    """A homogeneous linear diattenuator rot(-theta) diag(1, alpha) rot(theta) (polarization.py:199-231).  Departures: theta may be a
+    map; a scalar alpha outside [0, 1] raises ValueError (the reference asserts); a map of alpha is not inspected."""
+    if not _is_map(alpha) and not 0 <= alpha <= 1:
+        raise ValueError(f'alpha cannot be less than 0 or greater than 1, got: {alpha}')
+    return _generate(PP.DIATTENUATOR, [alpha, theta], ['alpha', 'theta'], shape, field, out_layout, out)
+
+
+def half_wave_plate(theta=0, shape=None, **kwargs):
+    """A half wave plate: linear_retarder(pi, ...) (polarization.py:234-251)."""
+    return linear_retarder(np.pi, theta=theta, shape=shape, **kwargs)
+
+
+def quarter_wave_plate(theta=0, shape=None, **kwargs):
+    """A quarter wave plate: linear_retarder(pi / 2, ...) (polarization.py:254-272)."""
+    return linear_retarder(np.pi / 2, theta=theta, shape=shape, **kwargs)
+
+
+def linear_polarizer(theta=0, shape=None, **kwargs):
+    """A linear polarizer: linear_diattenuator(0, ...) (polarization.py:275-293)."""
+    return linear_diattenuator(0, theta=theta, shape=shape, **kwargs)
+
+
+def vector_vortex_retarder(charge, theta, retardance=np.pi, rotate=0, *, identity_leakage=False, field=None, out_layout=None, out=None):
+    """A phase-only spatially-varying vector vortex retarder, Mawet et al. (2009) eq. 7 (polarization.py:296-346).  charge x theta is
+    formed in theta's precision before the cosine and sine, as the reference forms it.  Departures: theta is not modified (the
+    reference multiplies the caller's array in place); identity_leakage=True puts the -i cos(retardance / 2) term on both diagonal
+    elements as the paper does -- by default it lands on element (0,0) only, as in the reference."""
+    if not _is_map(theta):
+        raise TypeError('theta is the map of azimuthal angles (coordinates.cart_to_polar)')
+    return _generate(PP.VORTEX, [theta, retardance, rotate], ['theta', 'retardance', 'rotate'], None, field, out_layout, out, charge=charge,
+                     leak=identity_leakage)
+
+
+def pauli_spin_matrix(index, shape=None, *, out_layout=None, out=None):
+    """A Pauli spin matrix, CLY eq. 6.108 (polarization.py:410-452): the host's 2 x 2, or with shape= its copies in one launch."""
+    if index not in (0, 1, 2, 3):
+        raise ValueError(f'index should be 0,1,2, or 3. Got {index}')
+    m = np.array(PP.PAULI[index], dtype=config.precision_complex)
+    if shape is None and out is None:
+        return _host_tensor(m, _config_cdtype())
+    return _product([m], 'aos', out_layout, out, pix=None if shape is None else tuple(shape), dtype=_config_cdtype())
+
+
+def _is_small(x):
+    """a single 2 x 2 matrix or 2-vector: a constant of the chain"""
+    return tuple(x.shape) in ((2, 2), (2, 1), (2,))
+
+
+def _small_np(x):
+    if isinstance(x, torch.Tensor):
+        x = x.detach().resolve_conj().resolve_neg().cpu().numpy()
+    return np.asarray(x)
+
+
+def _product(operands, layout, out_layout, out, pix=None, dtype=None):
+    lay = PP.layout_code(layout)
+    olay = lay if out_layout is None else PP.layout_code(out_layout)
+    K = len(operands)
+    if not 1 <= K <= PP.MAX_CHAIN:
+        raise ValueError(f'between 1 and {PP.MAX_CHAIN} operands are taken, got {K}')
+    recs = (L.pm_jones_operand * K)()
+    keep, vector_tail = [], False
+    for i, x in enumerate(operands):
+        x = x if hasattr(x, 'shape') else np.asarray(x)
+        if _is_small(x):
+            a = _small_np(x).astype(np.complex128)
+            if a.shape != (2, 2):
+                if i != K - 1:
+                    raise ValueError('only the last operand may be a vector')
+                vector_tail = True
+            recs[i].map = None
+            for j, z in enumerate(a.reshape(-1)):
+                recs[i].c[2 * j], recs[i].c[2 * j + 1] = z.real, z.imag
+            keep.append(a)
+            continue
+        t, v = _jones_in(x, lay)
+        rows, cols, ld, ps, ncomp, p = v
+        if ncomp == 2:
+            if i != K - 1:
+                raise ValueError('only the last operand may be a vector')
+            vector_tail = True
+        if pix is None:
+            pix = tuple(p)
+        elif tuple(p) != tuple(pix):
+            raise ValueError(f'the operands differ in shape: {tuple(p)} and {tuple(pix)} pixels')
+        if dtype is None:
+            dtype = t.dtype
+        elif t.dtype != dtype:
+            t = t.to(dtype)
+            rows, cols, ld, ps, ncomp, p = _jones_view(t, lay)
+        keep.append(t)
+        recs[i].map, recs[i].ld, recs[i].pstride = t.data_ptr(), ld, ps
+    if pix is None and out is None:
+        # constants alone: the host's product
+        a = PP.chain([k.reshape(2, 2) if k.shape == (2, 2) else k.reshape(2, 1) for k in keep], vector_tail)
+        return _host_tensor(a, dtype or _config_cdtype())
+    if dtype is None:
+        dtype = out.dtype if out is not None else _config_cdtype()
+    ncomp = 2 if vector_tail else 4
+    if pix is None:
+        pix = tuple(out.shape[:-2]) if olay == PP.AOS else tuple(out.shape[1:])
+    o, (rows, cols, old, ops, _, _) = _jones_out(out, pix, ncomp, olay, dtype)
+    L.check(L.load().pm_jones_chain(L._COMPLEX_CODE[dtype], K, recs, lay, int(vector_tail), rows, cols, L.ptr(o), olay, old, ops, L.stream_ptr()))
+    return o
+
+
+def jones_product(*operands, layout='aos', out_layout=None, out=None):
+    """A_1 @ A_2 @ ... @ A_K for 1 <= K <= 6 in one launch, evaluated from the left as the reference's derot @ jones @ rot is.  An
+    operand is a Jones map in `layout` or a single 2 x 2 (a constant, passed by value); the last one may be a vector, (..., 2, 1),
+    (2, ...) planes or a single (2,) / (2, 1), and then so is the result.  Every map is read once and no intermediate product is
+    stored.  The result has the dtype of the first map; constants alone are multiplied on the host."""
+    return _product(list(operands), layout, out_layout, out)
+
+
+def _relayout(x, layout, out_layout, field, out, real_ok=True):
+    t, (rows, cols, ld, ps, ncomp, pix) = _jones_in(x, layout)
+    fptr, fld, fkind, f = None, 0, PP.FIELD_NONE, None
+    if field is not None:
+        f, fld, fkind = _field_map(field, t.dtype, pix, real_ok=real_ok)
+        fptr = L.ptr(f)
+    o, (_, _, old, ops, _, _) = _jones_out(out, pix, ncomp, out_layout, t.dtype)
+    L.check(L.load().pm_jones_scale(L._COMPLEX_CODE[t.dtype], ncomp, rows, cols, L.ptr(t), layout, ld, ps, fkind, fptr, fld, L.ptr(o), out_layout,
+                                    old, ops, L.stream_ptr()))
+    return o
+
+
+def to_planes(jones, *, out=None):
+    """aos (..., 2, 2) / (..., 2, 1) -> planes (4, ...) / (2, ...), bit for bit, one launch."""
+    return _relayout(jones, PP.AOS, PP.PLANES, None, out)
+
+
+def from_planes(planes, *, out=None):
+    """planes (4, ...) / (2, ...) -> aos (..., 2, 2) / (..., 2, 1), bit for bit, one launch."""
+    return _relayout(planes, PP.PLANES, PP.AOS, None, out)
+
+
+def apply_polarization_optic(field, pol_optic, *, layout='aos', out_layout=None, out=None):
+    """Apply a polarization optic, a Jones map, to a scalar field of the pixel grid's shape (polarization.py:555-578): field x J for
+    matrices or vectors, complex or real field, in one launch; out may be pol_optic when the layouts are equal.  A single 2 x 2 optic
+    is broadcast over the field in a launch of its own first (two launches, the broadcast optic is stored)."""
+    lay = PP.layout_code(layout)
+    olay = lay if out_layout is None else PP.layout_code(out_layout)
+    if _is_small(pol_optic) and lay == PP.AOS:
+        f = field if isinstance(field, torch.Tensor) else L.as_device(field)
+        dtype = f.dtype if f.is_complex() else L._COMPLEX_OF.get(f.dtype, torch.complex128)
+        k = _small_np(pol_optic).astype(np.complex128)
+        one = torch.empty((*f.shape, *((2, 2) if k.shape == (2, 2) else (2, 1))), dtype=dtype, device=L.device())
+        _product([k if k.ndim == 2 else k.reshape(2, 1)], 'aos', None, one)
+        return _relayout(one, PP.AOS, olay, f, out)
+    pix = PP.ncomp_of(tuple(pol_optic.shape), lay)[1]
+    if tuple(field.shape) == (*pix, 1, 1):
+        field = field.reshape(pix)
+    return _relayout(pol_optic, lay, olay, field, out)
+
+
+def broadcast_kron(a, b):
+    """The broadcast Kronecker product of two (..., 2, 2) arrays (polarization.py:349-376), (..., 4, 4).  Kept for the reference's
+    interface: a torch.einsum, not a kernel of this library -- jones_to_mueller does not form this array."""
+    a, b = L.as_device(a), L.as_device(b)
+    tmp = torch.einsum('...ik,...jl->...ijkl', a, b)
+    return tmp.reshape(*a.shape[:-2], a.shape[-2] * b.shape[-2], a.shape[-1] * b.shape[-1])
+
+
+def jones_to_mueller(jones, broadcast=True, *, layout='aos', out_layout=None, out=None):
+    """The Mueller matrix of a Jones matrix, CLY eq. 6.99 (polarization.py:379-407): the sixteen real elements of
+    Re(U (J* (x) J) U^H) per pixel as closed forms in the four components, one launch, (..., 4, 4) or with out_layout='planes'
+    (16, ...).  `broadcast` is accepted for the reference's signature; a single 2 x 2 is converted on the host with the same closed
+    form either way (departure: the reference's broadcast=False calls np.kron)."""
+    lay = PP.layout_code(layout)
+    olay = lay if out_layout is None else PP.layout_code(out_layout)
+    if lay == PP.AOS and tuple(jones.shape) == (2, 2) and out is None:
+        a = _small_np(jones)
+        if not np.iscomplexobj(a):
+            a = a.astype(config.precision_complex)
+        return L.as_device(PP.mueller(a))
+    t, (rows, cols, ld, ps, ncomp, pix) = _jones_in(jones, lay)
+    if ncomp != 4:
+        raise ValueError('jones_to_mueller takes Jones matrices, not vectors')
+    o, (_, _, old, ops, _, _) = _jones_out(out, pix, 16, olay, L._REAL_OF[t.dtype])
+    L.check(L.load().pm_jones_to_mueller(L._COMPLEX_CODE[t.dtype], rows, cols, L.ptr(t), lay, ld, ps, L.ptr(o), olay, old, ops, L.stream_ptr()))
+    return o
+
+
+def pauli_coefficients(jones, *, layout='aos', out=None):
+    """The Pauli coefficients c0, c1, c2, c3 of a Jones matrix (polarization.py:455-475): four complex maps, the planes of one
+    (4, ...) array written in one launch from one read of the Jones map.  A single 2 x 2 gives four host scalars."""
+    lay = PP.layout_code(layout)
+    if lay == PP.AOS and tuple(jones.shape) == (2, 2) and out is None:
+        return tuple(complex(c) for c in PP.pauli(_small_np(jones).astype(config.precision_complex)))
+    t, (rows, cols, ld, ps, ncomp, pix) = _jones_in(jones, lay)
+    if ncomp != 4:
+        raise ValueError('pauli_coefficients takes Jones matrices, not vectors')
+    o, (_, _, old, ops, _, _) = _jones_out(out, pix, 4, PP.PLANES, t.dtype)
+    L.check(L.load().pm_pauli_coefficients(L._COMPLEX_CODE[t.dtype], rows, cols, L.ptr(t), lay, ld, ps, L.ptr(o), old, ops, L.stream_ptr()))
+    return o[0], o[1], o[2], o[3]
